@@ -8,15 +8,20 @@ same line also carries `single_clip`: ONE clip sharded over the N ranks (BASELIN
 the temporal-conv borders + sequence/head-parallel DiT), timed in the same run, with halo bytes per rank and the strong-scaling
 efficiency against this run's own one-GPU clip time.
 
-`python bench.py --gpus N` launches its own N ranks (re-exec under torch.distributed.run on 127.0.0.1) when it was not
+`python bench.py --gpus N` launches its own N ranks (a child process under torch.distributed.run on 127.0.0.1) when it was not
 started by a launcher already; either way every rank asserts WORLD_SIZE == --gpus and that it owns a distinct GPU.
 
-Prints ONE JSON line (rank 0) with `roofline` (dominant kernel = implicit-GEMM conv on MFMA, achieved from HIP events
+A plain run sets up, warms up, times --steps steps and prints ONE JSON line (rank 0) with the headline (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step`).  `--dump-outputs DIR` also writes what the last timed step returned (rank 0's clip) as
+float32 .npy files: a fixed, seeded sample of the whole clip plus its first and last frames.  Everything below is measured only with
+`--full`.
+
+With `--full` the line also carries `roofline` (dominant kernel = implicit-GEMM conv on MFMA, achieved from HIP events
 recorded around every launch - in the timed region when the VAE runs one stream, in a one-stream pass of the same process right
 behind it when the timed region runs the product's two VAE streams, where an event pair would also span the other stream's
 kernels; the line says which) and `cpu_baseline` (the torch-CPU oracle timed
 on the host cores on a bounded sample = the full 42-layer model on BASELINE configs[0]'s 9x256x256 clip; rank 0,
-N=1 only), plus the PSNR of the HIP path against that oracle run.
+N=1 only), plus the PSNR of the HIP path against that oracle run, the timed variants and, with N > 1, `single_clip`.
 """
 import argparse
 import json
@@ -77,6 +82,31 @@ def frame_checksums(x):
     return out
 
 
+DUMP_SAMPLE = 1 << 22          # elements of the seeded whole-clip sample (16 MB as float32)
+DUMP_FRAME_MAX = 1 << 22       # a frame with more elements than this (a 720p frame has 2.76 M) is left to the sample
+
+
+def dump_outputs(out, d):
+    """--dump-outputs: what the last timed step returned, as float32 .npy under `d` (at most 48 MB): `output_sample` = the clip's
+    elements at DUMP_SAMPLE positions drawn from a fixed seed (sorted; the same positions for the same clip size), and
+    `output_first_frame` / `output_last_frame` = [1, 3, H, W] whole.  `out` is None on a rank of the single-clip mode that decoded no
+    frame: then nothing is written."""
+    import numpy as np
+    if out is None or out.numel() == 0:
+        return
+    os.makedirs(d, exist_ok=True)
+    flat = out.detach().reshape(-1)
+    g = torch.Generator(device="cpu").manual_seed(20240)
+    n = min(DUMP_SAMPLE, flat.numel())
+    idx = torch.randint(0, flat.numel(), (n,), generator=g).sort().values
+    arrays = {"output_sample": flat[idx.to(flat.device)]}
+    if out[:, :, 0].numel() <= DUMP_FRAME_MAX:
+        arrays["output_first_frame"] = out[:, :, 0]
+        arrays["output_last_frame"] = out[:, :, -1]
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), a.float().cpu().numpy())
+
+
 def cpu_baseline(text, v, t, s, seed, dev):
     """Oracle (clean-room port of the reference's diffusers CPU path) on a bounded sample, all host cores, fp32: the FULL
     model (42 DiT layers, same deterministic weights as the timed GPU run, read tensor-by-tensor from the GPU generator so
@@ -85,7 +115,8 @@ def cpu_baseline(text, v, t, s, seed, dev):
     from oracle import dit as odit
     from oracle.vae import OracleVAE
 
-    cores = min(os.cpu_count() or 1, 64)     # torch-CPU conv3d stops scaling (and oversubscribes) beyond ~64 threads
+    # torch-CPU conv3d stops scaling (and oversubscribes) beyond ~64 threads; never more than this process may use (affinity, OMP_NUM_THREADS)
+    cores = min(len(os.sched_getaffinity(0)), 64, int(os.environ.get("OMP_NUM_THREADS") or 64))
     torch.set_num_threads(cores)
     F, H, W = 9, 256, 256
     wv = weights.LazyStateDict(weights.vae_param_shapes(v), seed, dev, to="cpu")
@@ -109,10 +140,12 @@ def cpu_baseline(text, v, t, s, seed, dev):
 
 
 def relaunch_if_needed(args):
-    """`python bench.py --gpus N` (how the driver calls it) with no launcher: become N ranks, one per GPU."""
+    """`python bench.py --gpus N` (how the driver calls it) with no launcher: run N ranks, one per GPU, in a child launcher and leave
+    with its exit status (a child, not an exec: this process has already asked the HIP runtime for its devices)."""
     if args.gpus <= 1 or "RANK" in os.environ:
         return
     import socket
+    import subprocess
     n = torch.cuda.device_count()
     if n < args.gpus and not args.oversubscribe:
         raise SystemExit(f"bench.py: --gpus {args.gpus} but only {n} GPU(s) are visible")
@@ -123,7 +156,7 @@ def relaunch_if_needed(args):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush()
-    os.execvp(cmd[0], cmd)
+    raise SystemExit(subprocess.call(cmd))
 
 
 def main():
@@ -144,7 +177,7 @@ def main():
     ap.add_argument("--vae-streams", type=int, choices=[1, 2, 3, 4], default=None,
                     help="HIP streams the VAE's frame-batches alternate on (default: the product's, 2); 1 for the A/B")
     ap.add_argument("--timed-region-events", action="store_true",
-                    help="also record the per-launch HIP events inside the two-stream timed region (roofline.avg_launch_ms_timed_region); by "
+                    help="with --full, also record the per-launch HIP events inside the two-stream timed region (roofline.avg_launch_ms_timed_region); by "
                          "default the events are recorded only in the one-stream pass behind it, which is where the roofline is taken from")
     ap.add_argument("--no-variants", action="store_true", help="skip the extra (never headline) MXFP8 measurement of the N=1 line")
     ap.add_argument("--oversubscribe", action="store_true",
@@ -153,7 +186,14 @@ def main():
     ap.add_argument("--single-clip", action="store_true",
                     help="strong scaling: ONE clip sharded over all ranks (halo-exact VAE + Ulysses DiT, dove_amd.dist."
                          "process_video_sharded) instead of one clip per rank; not the driver's default")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: roofline (one-stream profiling pass), PMC replay, cpu_baseline + parity gates, "
+                         "variants and, with --gpus N > 1, the single-clip mode; a plain run measures only the timed steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step returned (rank 0) as float32 .npy files under DIR")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     relaunch_if_needed(args)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -222,7 +262,7 @@ def main():
         step()
     records = []
     two_stream_region = pipe.vae.n_streams >= 2 and not strong
-    if args.timed_region_events or not two_stream_region:
+    if args.full and (args.timed_region_events or not two_stream_region):
         ops.set_profiler(records)
     barrier()
     t0 = time.perf_counter()
@@ -235,7 +275,7 @@ def main():
     # chip with the other stream's kernels.  The roofline's per-launch durations therefore come from a ONE-stream pass of the same process,
     # right behind the timed region (same clip, same weights, same launches); the line carries both and says which is which.
     prof_records, prof_steps, prof_elapsed, prof_note = records, args.steps, elapsed, "the timed region (one HIP stream)"
-    if two_stream_region:
+    if args.full and two_stream_region:
         keep_streams, pipe.vae.n_streams = pipe.vae.n_streams, 1
         prof_records, prof_steps = [], max(1, min(args.steps, 3))
         step()
@@ -267,6 +307,8 @@ def main():
         assert out is None or (out.shape[0:2] == (1, 3) and out.shape[3:] == (args.height, args.width) and bool(torch.isfinite(out).all()))
     else:
         assert out.shape == (1, 3, args.frames, args.height, args.width) and bool(torch.isfinite(out).all())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, args.dump_outputs)
 
     def measure_single_clip():
         fault = os.environ.get("DOVE_BENCH_STRONG_FAULT", "")      # debug only (tests of the guard below): "raise:<rank>" / "hang:<rank>" / "corrupt:<rank>"
@@ -340,62 +382,63 @@ def main():
         macs = flops.clip_macs(v, t, args.frames, args.height, args.width)
         ms_step = elapsed / args.steps * 1e3
         value = (1 if strong else world) * args.steps * args.frames / elapsed
-        # dominant kernel = conv3x3_halo4x_kernel (VAE 3x3x3 / up-sampling 3x3 convs, ~half of the step).  achieved = sum(algorithmic FLOP)
-        # / sum(launch duration) over ITS launches inside the timed region (HIP events on the launch stream).
-        def agg(recs, col=5):
-            # col 5 = FLOPs the kernel actually issued, col 1 = the reference's algorithmic count (larger where the first-frame / sub-pixel
-            # weight sums skip duplicate taps): the roofline is priced on the ISSUED work, the algorithmic rate is reported next to it
-            fl = sum(r[col] for r in recs)
-            ms = sum(r[2].elapsed_time(r[3]) for r in recs)
-            return fl, ms
-        DOM = "conv3x3_halo4x_kernel"
-        dom = [r for r in prof_records if r[4] == DOM]
-        dom_fl, dom_ms = agg(dom)
-        tot_fl, tot_ms = agg(prof_records)
-        dom_fl_alg, _ = agg(dom, 1)
-        dom_timed = [r for r in records if r[4] == DOM]
-        dom_ms_timed = agg(dom_timed)[1]
-        by = {}
-        for key, _fl_alg, e0, e1, var, fl in prof_records:
-            k = f"{var}:cin{key[0]}_cout{key[1]}_taps{key[2]}"
-            a = by.setdefault(k, [0.0, 0.0, 0])
-            a[0] += fl
-            a[1] += e0.elapsed_time(e1)
-            a[2] += 1
-        top = sorted(by.items(), key=lambda kv: -kv[1][1])[:8]
-        achieved = dom_fl / (dom_ms * 1e-3) / 1e12 if dom_ms > 0 else 0.0
-        all_igemm = tot_fl / (tot_ms * 1e-3) / 1e12 if tot_ms > 0 else 0.0
-        # PMC-derived fields are NOT measured in this run: they are replayed from the committed summary of a separate
-        # `rocprofv3 --pmc` pass over this same command (tools/runs/gpu_pmc_bench.sh) and labelled as such
-        traffic = None
-        pmc_busy = None
-        pmc_src = None
-        pmc = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-        if os.path.exists(pmc):
-            with open(pmc) as f:
-                pj = json.load(f)
-            # the static summary is only replayed when it describes THIS build's launches: the dominant kernel must be in it under the
-            # name the library reports now, with the launch count per clip this run just observed (a kernel that was renamed, split or
-            # re-dispatched since the PMC pass makes the numbers stale - then the fields stay null and say why)
-            pk = pj.get("per_kernel", {}).get(DOM)
-            seen = len(dom) // max(prof_steps, 1)
-            from dove_amd.lib import kernel_source_sha256
-            tree = kernel_source_sha256()
-            if pj.get("kernel_source_sha256") != tree:
-                # the summary was measured on OTHER kernel code than this tree's (any edit of csrc/*.hip, csrc/*.h or the ABI header)
-                pmc_src = (f"profiles/pmc_traffic.json NOT replayed: it was collected on kernel sources {str(pj.get('kernel_source_sha256'))[:16]}, "
-                           f"this tree is {tree[:16]} - re-run tools/runs/gpu_pmc_bench.sh")
-                pj = None
-            elif pk is None or int(pk.get("launches", -1)) != seen:
-                pmc_src = (f"profiles/pmc_traffic.json NOT replayed: it holds {None if pk is None else pk.get('launches')} launches of {DOM} per clip, "
-                           f"this run made {seen} - re-run tools/runs/gpu_pmc_bench.sh")
-                pj = None
-        if os.path.exists(pmc) and pj is not None:
-            traffic = pj.get("per_kernel", {}).get(DOM, {}).get("hbm_bytes_per_launch")
-            pmc_busy = {"whole_step": pj.get("whole_step_mfma_busy_frac"), "per_kernel": pj.get("mfma_busy_frac_per_kernel"),
-                        "source": "profiles/pmc_traffic.json (static: separate rocprofv3 --pmc pass, not this run; same kernel sources: "
-                                  f"sha256 {tree[:16]})", "note": pj.get("note")}
-            pmc_src = "profiles/pmc_traffic.json (static: separate rocprofv3 --pmc FETCH_SIZE/WRITE_SIZE passes, not this run)"
+        if args.full:
+            # dominant kernel = conv3x3_halo4x_kernel (VAE 3x3x3 / up-sampling 3x3 convs, ~half of the step).  achieved = sum(algorithmic FLOP)
+            # / sum(launch duration) over ITS launches inside the timed region (HIP events on the launch stream).
+            def agg(recs, col=5):
+                # col 5 = FLOPs the kernel actually issued, col 1 = the reference's algorithmic count (larger where the first-frame / sub-pixel
+                # weight sums skip duplicate taps): the roofline is priced on the ISSUED work, the algorithmic rate is reported next to it
+                fl = sum(r[col] for r in recs)
+                ms = sum(r[2].elapsed_time(r[3]) for r in recs)
+                return fl, ms
+            DOM = "conv3x3_halo4x_kernel"
+            dom = [r for r in prof_records if r[4] == DOM]
+            dom_fl, dom_ms = agg(dom)
+            tot_fl, tot_ms = agg(prof_records)
+            dom_fl_alg, _ = agg(dom, 1)
+            dom_timed = [r for r in records if r[4] == DOM]
+            dom_ms_timed = agg(dom_timed)[1]
+            by = {}
+            for key, _fl_alg, e0, e1, var, fl in prof_records:
+                k = f"{var}:cin{key[0]}_cout{key[1]}_taps{key[2]}"
+                a = by.setdefault(k, [0.0, 0.0, 0])
+                a[0] += fl
+                a[1] += e0.elapsed_time(e1)
+                a[2] += 1
+            top = sorted(by.items(), key=lambda kv: -kv[1][1])[:8]
+            achieved = dom_fl / (dom_ms * 1e-3) / 1e12 if dom_ms > 0 else 0.0
+            all_igemm = tot_fl / (tot_ms * 1e-3) / 1e12 if tot_ms > 0 else 0.0
+            # PMC-derived fields are NOT measured in this run: they are replayed from the committed summary of a separate
+            # `rocprofv3 --pmc` pass over this same command (tools/runs/gpu_pmc_bench.sh) and labelled as such
+            traffic = None
+            pmc_busy = None
+            pmc_src = None
+            pmc = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+            if os.path.exists(pmc):
+                with open(pmc) as f:
+                    pj = json.load(f)
+                # the static summary is only replayed when it describes THIS build's launches: the dominant kernel must be in it under the
+                # name the library reports now, with the launch count per clip this run just observed (a kernel that was renamed, split or
+                # re-dispatched since the PMC pass makes the numbers stale - then the fields stay null and say why)
+                pk = pj.get("per_kernel", {}).get(DOM)
+                seen = len(dom) // max(prof_steps, 1)
+                from dove_amd.lib import kernel_source_sha256
+                tree = kernel_source_sha256()
+                if pj.get("kernel_source_sha256") != tree:
+                    # the summary was measured on OTHER kernel code than this tree's (any edit of csrc/*.hip, csrc/*.h or the ABI header)
+                    pmc_src = (f"profiles/pmc_traffic.json NOT replayed: it was collected on kernel sources {str(pj.get('kernel_source_sha256'))[:16]}, "
+                               f"this tree is {tree[:16]} - re-run tools/runs/gpu_pmc_bench.sh")
+                    pj = None
+                elif pk is None or int(pk.get("launches", -1)) != seen:
+                    pmc_src = (f"profiles/pmc_traffic.json NOT replayed: it holds {None if pk is None else pk.get('launches')} launches of {DOM} per clip, "
+                               f"this run made {seen} - re-run tools/runs/gpu_pmc_bench.sh")
+                    pj = None
+            if os.path.exists(pmc) and pj is not None:
+                traffic = pj.get("per_kernel", {}).get(DOM, {}).get("hbm_bytes_per_launch")
+                pmc_busy = {"whole_step": pj.get("whole_step_mfma_busy_frac"), "per_kernel": pj.get("mfma_busy_frac_per_kernel"),
+                            "source": "profiles/pmc_traffic.json (static: separate rocprofv3 --pmc pass, not this run; same kernel sources: "
+                                      f"sha256 {tree[:16]})", "note": pj.get("note")}
+                pmc_src = "profiles/pmc_traffic.json (static: separate rocprofv3 --pmc FETCH_SIZE/WRITE_SIZE passes, not this run)"
         fp8_parts = (["qkv/out/ff linears"] if args.dit_linear == "mxfp8" else []) + (["attention"] if args.dit_attention == "mxfp8" else [])
         headline = not fp8_parts
         res = {
@@ -416,32 +459,35 @@ def main():
             "ranks": {"world_size_observed": observed_world, "gpus": gpu_ids,
                       "busy_s_per_rank": per_rank, "slowest_over_fastest": max(per_rank) / min(per_rank)},
             "whole_path_tflops_per_gpu": macs["flop"] * args.steps / elapsed / 1e12,
-            # the same with the taps the weight-summed conv forms skip taken out (what the matrix pipes were actually asked to do)
-            "whole_path_tflops_issued_per_gpu": (macs["flop"] - sum(r[1] - r[5] for r in prof_records) / max(prof_steps, 1)) * args.steps / elapsed / 1e12,
-            "roofline": {"bound": "mfma", "kernel": DOM + " (persistent LDS-halo implicit-GEMM 3x3(x3) conv, bf16 MFMA 16x16x32)",
-                         "achieved": achieved, "peak": MFMA_BF16_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": achieved / MFMA_BF16_PEAK_TFLOPS,
-                         "traffic": traffic, "traffic_source": pmc_src, "launches": len(dom) // max(prof_steps, 1), "avg_launch_ms": dom_ms / max(len(dom), 1),
-                         "launch_is": "one dove_conv_igemm_bf16 call = ONE kernel launch at every shape of the untiled clip (dove_conv_partial_launches "
-                                      "is 0 for them: profiles/pmc_traffic.json kernel_launches == launches); only the tiled variant's 240 x 360 "
-                                      "tile class adds a second launch (conv3x3_halo4x_kernel<..., 1>) for its partial last tile column",
-                         "durations_from": prof_note,
-                         "avg_launch_ms_timed_region": (dom_ms_timed / len(dom_timed)) if dom_timed else None,
-                         "avg_launch_gflop": dom_fl / max(len(dom), 1) / 1e9,
-                         "flops_counted": "MFMA work actually issued; the reference's formulation of the same launches is "
-                                          f"{dom_fl_alg / max(dom_fl, 1):.4f} x that (first-frame temporal sums, sub-pixel upsample convs skip duplicate taps)",
-                         "achieved_algorithmic": dom_fl_alg / (dom_ms * 1e-3) / 1e12 if dom_ms > 0 else 0.0,
-                         "share_of_step_time": dom_ms / (prof_elapsed * 1e3),
-                         # SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE/8 * 1024 SIMDs) from profiles/pmc_traffic.json
-                         # (separate rocprofv3 --pmc pass over this command, tools/runs/gpu_pmc_bench.sh)
-                         "mfma_pipe_busy_frac_pmc": pmc_busy,
-                         "all_igemm_kernels": {"achieved": all_igemm, "frac": all_igemm / MFMA_BF16_PEAK_TFLOPS,
-                                               "share_of_step_time": tot_ms / (prof_elapsed * 1e3), "launches": len(prof_records) // max(prof_steps, 1)},
-                         "top_classes": {k: {"ms": a[1] / prof_steps, "tflops": a[0] / (a[1] * 1e-3) / 1e12, "launches": a[2] // prof_steps}
-                                         for k, a in top}},
             "model_build_s": t_build,
             # peak of torch's allocator over the run so far (weights 11.6 GB + the clip's activations; two VAE streams = two pools)
             "hbm_peak_allocated_gb": torch.cuda.max_memory_allocated(dev) / 1e9, "hbm_peak_reserved_gb": torch.cuda.max_memory_reserved(dev) / 1e9,
         }
+        if args.full:
+            res.update({
+                # the same with the taps the weight-summed conv forms skip taken out (what the matrix pipes were actually asked to do)
+                "whole_path_tflops_issued_per_gpu": (macs["flop"] - sum(r[1] - r[5] for r in prof_records) / max(prof_steps, 1)) * args.steps / elapsed / 1e12,
+                "roofline": {"bound": "mfma", "kernel": DOM + " (persistent LDS-halo implicit-GEMM 3x3(x3) conv, bf16 MFMA 16x16x32)",
+                             "achieved": achieved, "peak": MFMA_BF16_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": achieved / MFMA_BF16_PEAK_TFLOPS,
+                             "traffic": traffic, "traffic_source": pmc_src, "launches": len(dom) // max(prof_steps, 1), "avg_launch_ms": dom_ms / max(len(dom), 1),
+                             "launch_is": "one dove_conv_igemm_bf16 call = ONE kernel launch at every shape of the untiled clip (dove_conv_partial_launches "
+                                          "is 0 for them: profiles/pmc_traffic.json kernel_launches == launches); only the tiled variant's 240 x 360 "
+                                          "tile class adds a second launch (conv3x3_halo4x_kernel<..., 1>) for its partial last tile column",
+                             "durations_from": prof_note,
+                             "avg_launch_ms_timed_region": (dom_ms_timed / len(dom_timed)) if dom_timed else None,
+                             "avg_launch_gflop": dom_fl / max(len(dom), 1) / 1e9,
+                             "flops_counted": "MFMA work actually issued; the reference's formulation of the same launches is "
+                                              f"{dom_fl_alg / max(dom_fl, 1):.4f} x that (first-frame temporal sums, sub-pixel upsample convs skip duplicate taps)",
+                             "achieved_algorithmic": dom_fl_alg / (dom_ms * 1e-3) / 1e12 if dom_ms > 0 else 0.0,
+                             "share_of_step_time": dom_ms / (prof_elapsed * 1e3),
+                             # SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE/8 * 1024 SIMDs) from profiles/pmc_traffic.json
+                             # (separate rocprofv3 --pmc pass over this command, tools/runs/gpu_pmc_bench.sh)
+                             "mfma_pipe_busy_frac_pmc": pmc_busy,
+                             "all_igemm_kernels": {"achieved": all_igemm, "frac": all_igemm / MFMA_BF16_PEAK_TFLOPS,
+                                                   "share_of_step_time": tot_ms / (prof_elapsed * 1e3), "launches": len(prof_records) // max(prof_steps, 1)},
+                             "top_classes": {k: {"ms": a[1] / prof_steps, "tflops": a[0] / (a[1] * 1e-3) / 1e12, "launches": a[2] // prof_steps}
+                                             for k, a in top}},
+            })
         if (args.frames, args.height, args.width) != (33, 720, 1280):
             res["note"] = "not BASELINE.json's headline clip size (33x720x1280): a side measurement"
         if args.oversubscribe:
@@ -452,7 +498,7 @@ def main():
                                     "communicators": getattr(pipe.vae, "last_halo_stats_decode", {}).get("communicators")}
         if args.layers is not None:
             res["invalid"] = "debug run with a truncated DiT"
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             base, (svid, snoise, sref, strace) = cpu_baseline(text, v, t, s, 1234, dev)
             res["cpu_baseline"] = base
             # PSNR of the SAME pipeline object the timed region ran (full depth, same weights) vs the fp32 oracle on that sample
@@ -485,7 +531,7 @@ def main():
                 res["invalid"] = f"parity gate failed: {psnr_in:.2f} dB over un-saturated pixels (< 35 dB)"
             if not res["stage_parity"]["passed"]:
                 res["invalid"] = f"stage parity gate failed: {se}"
-        if world == 1 and headline and not args.no_variants:
+        if args.full and world == 1 and headline and not args.no_variants:
             res["variants"] = []
             vsteps = max(1, min(args.steps, 5))
 
@@ -595,7 +641,7 @@ def main():
             ent["clip_flop_ratio_tiled_over_untiled"] = whole_ratio
             ent["throughput_vs_untiled_times_flop_ratio"] = (vsteps * args.frames / tv) / (value / whole_ratio)
             res["variants"].append(ent)
-        if world == 1 and headline and not args.no_variants and args.layers is None:
+        if args.full and world == 1 and headline and not args.no_variants and args.layers is None:
             # BASELINE configs[4] measured in the SAME run on the same clip (never the headline): the DiT rebuilt with MXFP8 linears +
             # attention (same seed), the VAE object shared.  PSNR gates of this variant: tests/test_parity_gpu.py::test_mxfp8_dit_psnr_gate
             del pipe.transformer
@@ -624,7 +670,7 @@ def main():
     # has run on RCCL with one rank only (no multi-GPU box was available to the builder; tests: gloo, R = 2 / 4 / 8 processes on one GPU), so it
     # must not be able to take the weak-scaling line - measured and assembled above - down with it: an exception on any rank, or a
     # collective that never returns, ends in `single_clip: {"error": ...}` on the ONE line rank 0 prints, and every rank leaves with 0 ----
-    if use_dist and world > 1 and not strong:
+    if args.full and use_dist and world > 1 and not strong:
         import threading
         limit = float(os.environ.get("DOVE_BENCH_STRONG_TIMEOUT", 180.0 + 6.0 * elapsed * (1.0 + args.warmup / max(args.steps, 1))))
 

@@ -124,7 +124,7 @@ def _bench_line(env_extra):
     env.pop("RANK", None)
     env.pop("WORLD_SIZE", None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--oversubscribe", "--layers", "1", "--steps", "1", "--warmup", "1",
-           "--frames", "17", "--height", "128", "--width", "192", "--no-variants"]
+           "--frames", "17", "--height", "128", "--width", "192", "--no-variants", "--full"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=420, cwd=ROOT)
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert p.returncode == 0 and len(lines) == 1, (p.returncode, p.stdout[-2000:], p.stderr[-3000:])
