@@ -4,12 +4,14 @@ Every flag of the reference's parser (ref :507-554) is accepted: ``--input_dir -
 --lora_path --output_path --fps --dtype --seed --upscale_mode --upscale --noise_step --sr_noise_step --is_cpu_offload --is_vae_st
 --png_save --save_format --tile_size_hw --overlap_hw --chunk_len --overlap_t``.  ``--fps`` / ``--save_format`` describe the mp4
 container the reference writes with imageio - frame files carry neither, so they are accepted and reported; ``--is_cpu_offload``
-calls ``pipe.enable_sequential_cpu_offload()`` like the reference (a no-op with 288 GB of HBM); ``--eval_metrics`` knows ``psnr``
-(the pyiqa metrics are out of scope); ``--dtype`` other than bfloat16 is refused.  Inputs are PNG folders
+calls ``pipe.enable_sequential_cpu_offload()`` like the reference (a no-op with 288 GB of HBM); ``--eval_metrics`` knows ``psnr`` and
+``ssim``, computed on the GPU (dove_amd.metrics) from the uint8 frames written to disk against ``--gt_dir/<clip>``, as the reference's
+``eval_metrics.py`` scores the saved files; the per-clip values go to ``metrics_<names>.json`` in ``--output_path`` (the reference's
+structure, ref :755-776); the network metrics of pyiqa (lpips, dists, clipiqa, ...) are not provided; ``--dtype`` other than bfloat16 is refused.  Inputs are PNG folders
 or ``.npy`` clips (uint8 [F,H,W,3]) because H.264 decoding (decord) is outside the accelerated path; outputs are PNG
 folders or ``.npy``.  ``--random_init`` builds the CogVideoX1.5-5B architecture with synthetic weights (no checkpoint is
-available offline).  Metrics (pyiqa) are not provided; ``--eval_psnr_dir`` computes plain PSNR (10*log10(1/MSE), per-frame
-mean) against ground-truth folders."""
+available offline).  ``--eval_psnr_dir`` computes plain PSNR (10*log10(1/MSE), per-frame mean) on the CPU against ground-truth folders; with it,
+``psnr`` in ``--eval_metrics`` is that value and the other metrics use ``--gt_dir`` (or those folders without ``--gt_dir``)."""
 from __future__ import annotations
 
 import argparse
@@ -27,7 +29,7 @@ def main(argv=None):
     ap.add_argument("--random_init", action="store_true")
     ap.add_argument("--output_path", type=str, default="./results")
     ap.add_argument("--gt_dir", type=str, default=None, help="ground-truth folders / .npy clips for --eval_metrics (ref :511)")
-    ap.add_argument("--eval_metrics", type=str, default="", help="'psnr' (ref :513; the pyiqa metrics ssim,lpips,... are out of scope)")
+    ap.add_argument("--eval_metrics", type=str, default="", help="any of 'psnr,ssim' (ref :513), on the GPU; the network metrics of pyiqa (lpips, ...) are not provided")
     ap.add_argument("--fps", type=int, default=16, help="accepted like the reference (ref :521): frame files (PNG / .npy) carry no frame rate")
     ap.add_argument("--dtype", type=str, default="bfloat16")
     ap.add_argument("--seed", type=int, default=42)
@@ -51,13 +53,16 @@ def main(argv=None):
     if args.dtype != "bfloat16":
         raise ValueError(f"--dtype {args.dtype}: the HIP path computes in bfloat16 (the reference's default, ref :525); float16 / float32 "
                          "are not implemented (INTEGRATION.md, 'dtype')")
-    metrics = [m for m in args.eval_metrics.split(",") if m]
-    if any(m != "psnr" for m in metrics):
-        raise NotImplementedError(f"--eval_metrics {args.eval_metrics}: only 'psnr' is computed here; the pyiqa metrics are outside the path")
+    metrics = [m.strip().lower() for m in args.eval_metrics.split(",") if m.strip()]
+    if any(m not in ("psnr", "ssim") for m in metrics):
+        raise NotImplementedError(f"--eval_metrics {args.eval_metrics}: only 'psnr' and 'ssim' are computed here; the other pyiqa metrics "
+                                  "need network weights and are outside the path")
     if metrics and not (args.gt_dir or args.eval_psnr_dir):
-        raise ValueError("--eval_metrics psnr needs --gt_dir")
-    if args.gt_dir and not args.eval_psnr_dir and metrics:
-        args.eval_psnr_dir = args.gt_dir
+        raise ValueError(f"--eval_metrics {args.eval_metrics} needs --gt_dir")
+    # with --eval_psnr_dir, PSNR stays on that flag's CPU path (against its folders, as before); the rest runs on the GPU against
+    # --gt_dir (or the --eval_psnr_dir folders when --gt_dir is not given)
+    gpu_metrics = [m for m in metrics if not (m == "psnr" and args.eval_psnr_dir)]
+    metrics_gt = args.gt_dir or args.eval_psnr_dir
 
     from safetensors.torch import load_file
 
@@ -105,6 +110,7 @@ def main(argv=None):
         with open(args.input_json) as f:
             prompts = json.load(f)
     psnrs = {}
+    scores = {m: [] for m in metrics}                                     # per clip, in clip order (ref :647-656, :755-776)
     for name in names:
         prompt = prompts.get(name, "")
         frames = prepost.load_frames(os.path.join(args.input_dir, name))
@@ -132,8 +138,23 @@ def main(argv=None):
             mse = ((gt - pr) ** 2).flatten(1).mean(1)
             psnrs[name] = float((10 * torch.log10(1.0 / (mse + 1e-8))).mean())
             print(f"[{name}] PSNR={psnrs[name]:.4f}")
+        if gpu_metrics:
+            from .metrics import clip_metrics
+            gt = prepost.load_frames(os.path.join(metrics_gt, name))
+            vals = clip_metrics(frames_out, gt, gpu_metrics)
+            for m in gpu_metrics:
+                print(f"[{name}] {m.upper()}={vals[m]:.4f}")
+        for m in metrics:
+            scores[m].append(vals[m] if m in gpu_metrics else psnrs[name])
     if psnrs:
         print(f"=== Overall Average PSNR: {sum(psnrs.values()) / len(psnrs):.4f} ===")
+    if metrics:
+        import json
+        average = {m: sum(v) / len(v) for m, v in scores.items()}
+        for m in gpu_metrics:
+            print(f"=== Overall Average {m.upper()}: {average[m]:.4f} ===")
+        with open(os.path.join(args.output_path, "metrics_" + "_".join(metrics) + ".json"), "w") as f:
+            json.dump({"per_sample": scores, "average": average, "count": len(names)}, f, indent=2)
     print("All videos processed.")
 
 

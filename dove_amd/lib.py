@@ -11,7 +11,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libdove_hip.so")
 _lib = None
 
-F32, BF16 = 0, 1
+F32, BF16, U8 = 0, 1, 2
+METRIC_PSNR, METRIC_SSIM, METRIC_RGB_TO_Y = 1, 2, 4           # dove_fr_metrics flags
 
 
 class ConvDesc(C.Structure):
@@ -45,6 +46,12 @@ class ModelConfig(C.Structure):
                [(n, C.c_int) for n in ("dit_heads", "dit_head_dim", "dit_num_layers", "dit_in_channels", "dit_out_channels", "dit_patch",
                                        "dit_patch_t", "dit_text_dim", "dit_time_embed_dim", "dit_max_text", "dit_flip_sin_to_cos")] + \
                [("dit_norm_eps", C.c_float), ("dit_freq_shift", C.c_float)]
+
+
+class ImageView(C.Structure):
+    """dove_image_view (include/dove_hip.h): a strided 4-D view, element (n, c, y, x) at data + n*sn + c*sc + y*sh + x*sw elements."""
+    _fields_ = [("data", C.c_void_p), ("dtype", C.c_int), ("reserved", C.c_int),
+                ("sn", C.c_longlong), ("sc", C.c_longlong), ("sh", C.c_longlong), ("sw", C.c_longlong)]
 
 
 class DitAux(C.Structure):
@@ -119,6 +126,7 @@ SIGNATURES = {
     "dove_conv_out_gather_cl": [_VP, _LL, _I, _I, _I, _I, _VP, _VP, _I, _VP],
     "dove_tile_gather_bf16": [_VP, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_int), C.POINTER(C.c_int), _I, _VP, _VP],
     "dove_linear_mxfp8": [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _LL, _I, _I, _LL, _LL, _LL, _I, _VP],
+    "dove_fr_metrics": [C.POINTER(ImageView), C.POINTER(ImageView), _I, _I, _I, _I, _I, _VP, C.c_size_t, _VP, _VP],
 }
 PLAIN = {"dove_last_error": (C.c_char_p, []), "dove_abi_version": (C.c_int, []), "dove_comm_destroy": (None, [C.c_void_p]),
          "dove_conv_gn_partial_rows": (C.c_longlong, [C.POINTER(ConvDesc)]),
@@ -132,7 +140,8 @@ PLAIN = {"dove_last_error": (C.c_char_p, []), "dove_abi_version": (C.c_int, []),
          "dove_get_option": (C.c_longlong, [_VP, _I]),
          "dove_comm_useful_ranks": (C.c_int, [_VP, _I, _I]),
          "dove_workspace_bytes": (C.c_size_t, [_VP, _I, _I, _I]),
-         "dove_workspace_high_water": (C.c_size_t, [_VP])}
+         "dove_workspace_high_water": (C.c_size_t, [_VP]),
+         "dove_fr_metrics_workspace_bytes": (C.c_size_t, [_I, _I, _I])}
 
 
 def kernel_source_sha256() -> str:

@@ -640,6 +640,34 @@ def postprocess_u8(video: torch.Tensor, Fo: int, Ho: int, Wo: int) -> torch.Tens
     return out
 
 
+def _image_view(t: torch.Tensor) -> L.ImageView:
+    codes = {torch.float32: L.F32, torch.bfloat16: L.BF16, torch.uint8: L.U8}
+    if t.dtype not in codes:
+        raise TypeError(f"fr_metrics reads float32 / bfloat16 / uint8 images, got {t.dtype}")
+    v = L.ImageView()
+    v.data, v.dtype = t.data_ptr(), codes[t.dtype]
+    v.sn, v.sc, v.sh, v.sw = t.stride()
+    return v
+
+
+def fr_metrics(pred: torch.Tensor, ref: torch.Tensor, flags: int) -> torch.Tensor:
+    """pred, ref: [N,C,H,W] views (any strides, no copy) -> fp64 [N,2] {PSNR dB, SSIM} on the device (csrc/metrics.hip; NaN for a
+    metric ``flags`` does not ask for)."""
+    if pred.dim() != 4 or pred.shape != ref.shape:
+        raise ValueError(f"fr_metrics: pred {tuple(pred.shape)} and ref {tuple(ref.shape)} must be the same [N,C,H,W] shape")
+    if not (pred.is_cuda and ref.is_cuda) or pred.device != ref.device:
+        raise RuntimeError("fr_metrics needs both images on the same HIP device (`cuda`); there is no CPU path")
+    N, Cc, H, W = pred.shape
+    lib = L.load()
+    with torch.cuda.device(pred.device):
+        ws = torch.empty(max(int(lib.dove_fr_metrics_workspace_bytes(N, H, W)), 8), dtype=torch.uint8, device=pred.device)
+        out = torch.empty(N, 2, dtype=torch.float64, device=pred.device)
+        pv, rv = _image_view(pred), _image_view(ref)
+        L.check(lib.dove_fr_metrics(C.byref(pv), C.byref(rv), N, Cc, H, W, flags, L.ptr(ws), ws.numel(), L.ptr(out), L.stream_ptr()),
+                "dove_fr_metrics")
+    return out
+
+
 # ---- MXFP8 linears (BASELINE configs[4]; csrc/mxfp8.hip) ------------------------------------------------------------------
 @dataclass
 class PackedMx:

@@ -279,6 +279,27 @@ int dove_blend_edge_bf16(const void* a, void* b, int T, int Ha, int Wa, int Hb, 
 int dove_preprocess_u8(const void* frames, int F0, int H0, int W0, int pad_f, int pad_h, int pad_w, int upscale, void* out,
                        int out_dtype, void* stream);
 int dove_postprocess_u8(const void* video, int dtype, int F, int H, int W, int Fo, int Ho, int Wo, void* out, void* stream);
+
+/* Full-reference metrics of the reference's evaluation step (eval_metrics.py; pyiqa 'psnr' and 'ssim' defaults; INTEGRATION.md 'Metrics'):
+ * per image n of a batch, out[n][0] = PSNR in dB and out[n][1] = SSIM (fp64, device memory; NaN for a metric not asked for).
+ * Each input is a strided view: element (n, c, y, x) is at data + n*sn + c*sc + y*sh + x*sw elements, so [F,H,W,3] u8 frames, [3,F,H,W]
+ * decoder output and border / resolution crops (a pointer offset plus a smaller h x w) are read in place.  dtype: DOVE_F32, DOVE_BF16, or
+ * DOVE_U8 (read as value / 255).  flags: DOVE_METRIC_PSNR and/or DOVE_METRIC_SSIM, optionally DOVE_METRIC_RGB_TO_Y (eval_metrics.py
+ * --test_y_channel: y = 0.257 r + 0.504 g + 0.098 b + 0.0625 before both metrics; needs channels == 3).  channels: 1 or 3; SSIM needs
+ * h, w >= 11.  ws: device scratch of dove_fr_metrics_workspace_bytes(n, h, w) bytes.  Deterministic: two calls give identical bits. */
+#define DOVE_U8 2
+#define DOVE_METRIC_PSNR 1
+#define DOVE_METRIC_SSIM 2
+#define DOVE_METRIC_RGB_TO_Y 4
+typedef struct dove_image_view {
+  const void* data;
+  int dtype;
+  int reserved;
+  long long sn, sc, sh, sw;
+} dove_image_view;
+size_t dove_fr_metrics_workspace_bytes(int n, int h, int w);
+int dove_fr_metrics(const dove_image_view* pred, const dove_image_view* ref, int n, int channels, int h, int w, int flags, void* ws,
+                    size_t ws_bytes, double* out, void* stream);
 /* M = 1 linear with optional SiLU on the input (time_embedding MLP, norm*.linear modulation vectors) */
 int dove_gemv_bf16(const void* W, const float* bias, const float* x, int in_features, int out_features, int act_in,
                    float* y, void* stream);
