@@ -2,7 +2,8 @@
 
 Every flag of the reference's parser (ref :507-554) is accepted: ``--input_dir --input_json --gt_dir --eval_metrics --model_path
 --lora_path --output_path --fps --dtype --seed --upscale_mode --upscale --noise_step --sr_noise_step --is_cpu_offload --is_vae_st
---png_save --save_format --tile_size_hw --overlap_hw --chunk_len --overlap_t``.  ``--fps`` / ``--save_format`` describe the mp4
+--png_save --save_format --tile_size_hw --overlap_hw --chunk_len --overlap_t``; ``--color_fix {none,wavelet,adain}`` (not a flag of the reference's script: its
+``finetune/scripts/color_fix_util.py`` on the GPU, dove_amd.colorfix) fixes every output frame against the clip's upscaled input.  ``--fps`` / ``--save_format`` describe the mp4
 container the reference writes with imageio - frame files carry neither, so they are accepted and reported; ``--is_cpu_offload``
 calls ``pipe.enable_sequential_cpu_offload()`` like the reference (a no-op with 288 GB of HBM); ``--eval_metrics`` knows ``psnr`` and
 ``ssim``, computed on the GPU (dove_amd.metrics) from the uint8 frames written to disk against ``--gt_dir/<clip>``, as the reference's
@@ -46,6 +47,9 @@ def main(argv=None):
     ap.add_argument("--chunk_len", type=int, default=0)
     ap.add_argument("--overlap_t", type=int, default=8)
     ap.add_argument("--eval_psnr_dir", type=str, default=None)
+    ap.add_argument("--color_fix", type=str, default="none", choices=("none", "wavelet", "adain"),
+                    help="colour-fix every output frame against the clip's upscaled input on the GPU (dove_amd.colorfix; the reference's "
+                         "color_fix_util); saved and scored frames are the fixed ones")
     ap.add_argument("--num_layers", type=int, default=None, help="debug (with --random_init): fewer DiT layers than the 42 of CogVideoX1.5-5B")
     ap.add_argument("--prompt_embedding", type=str,
                     default="pretrained_models/prompt_embeddings/e3b0c44298fc1c149afbf4c8996fb92427ae41e4649b934ca495991b7852b855.safetensors")
@@ -98,6 +102,10 @@ def main(argv=None):
     if args.is_vae_st:
         pipe.vae.enable_slicing()
         pipe.vae.enable_tiling()
+    color_fix = None if args.color_fix == "none" else args.color_fix
+    if color_fix:
+        print(f"[dove_amd] --color_fix {color_fix}: output frames are colour-fixed against the upscaled input "
+              f"(--upscale_mode {args.upscale_mode}, x{args.upscale}) before they are saved and scored")
     overlap_t = args.overlap_t if args.chunk_len > 0 else 0
     os.makedirs(args.output_path, exist_ok=True)
     names = sorted(n for n in os.listdir(args.input_dir)
@@ -125,7 +133,10 @@ def main(argv=None):
                                   sr_noise_step=args.sr_noise_step, empty_prompt_embedding=emb)
             tiling.stitch(out, wc, piece, region)
         tiling.check_coverage(wc)
-        frames_out = prepost.postprocess_frames(out, pad_f, pad_h, pad_w)       # the reference crops pad*4 (ref :731)
+        if color_fix:
+            frames_out = prepost.postprocess_frames(out, pad_f, pad_h, pad_w, color_fix=color_fix, source=video)
+        else:
+            frames_out = prepost.postprocess_frames(out, pad_f, pad_h, pad_w)   # the reference crops pad*4 (ref :731)
         stem = name[:-4] if name.lower().endswith(".npy") else name
         if args.png_save:
             prepost.save_frames_as_png(frames_out, os.path.join(args.output_path, stem))

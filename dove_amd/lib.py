@@ -13,6 +13,7 @@ _lib = None
 
 F32, BF16, U8 = 0, 1, 2
 METRIC_PSNR, METRIC_SSIM, METRIC_RGB_TO_Y = 1, 2, 4           # dove_fr_metrics flags
+COLORFIX_WAVELET, COLORFIX_ADAIN, COLORFIX_CLAMP = 1, 2, 1    # dove_color_fix modes / flag
 
 
 class ConvDesc(C.Structure):
@@ -127,6 +128,8 @@ SIGNATURES = {
     "dove_tile_gather_bf16": [_VP, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_int), C.POINTER(C.c_int), _I, _VP, _VP],
     "dove_linear_mxfp8": [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _LL, _I, _I, _LL, _LL, _LL, _I, _VP],
     "dove_fr_metrics": [C.POINTER(ImageView), C.POINTER(ImageView), _I, _I, _I, _I, _I, _VP, C.c_size_t, _VP, _VP],
+    "dove_color_fix": [C.POINTER(ImageView), _F, _F, C.POINTER(ImageView), _F, _F, _I, _I, _I, _I, _I, C.POINTER(ImageView), _VP,
+                       C.c_size_t, _VP],
 }
 PLAIN = {"dove_last_error": (C.c_char_p, []), "dove_abi_version": (C.c_int, []), "dove_comm_destroy": (None, [C.c_void_p]),
          "dove_conv_gn_partial_rows": (C.c_longlong, [C.POINTER(ConvDesc)]),
@@ -141,7 +144,8 @@ PLAIN = {"dove_last_error": (C.c_char_p, []), "dove_abi_version": (C.c_int, []),
          "dove_comm_useful_ranks": (C.c_int, [_VP, _I, _I]),
          "dove_workspace_bytes": (C.c_size_t, [_VP, _I, _I, _I]),
          "dove_workspace_high_water": (C.c_size_t, [_VP]),
-         "dove_fr_metrics_workspace_bytes": (C.c_size_t, [_I, _I, _I])}
+         "dove_fr_metrics_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
+         "dove_color_fix_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I])}
 
 
 def kernel_source_sha256() -> str:

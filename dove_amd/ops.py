@@ -643,7 +643,7 @@ def postprocess_u8(video: torch.Tensor, Fo: int, Ho: int, Wo: int) -> torch.Tens
 def _image_view(t: torch.Tensor) -> L.ImageView:
     codes = {torch.float32: L.F32, torch.bfloat16: L.BF16, torch.uint8: L.U8}
     if t.dtype not in codes:
-        raise TypeError(f"fr_metrics reads float32 / bfloat16 / uint8 images, got {t.dtype}")
+        raise TypeError(f"image views are float32 / bfloat16 / uint8, got {t.dtype}")
     v = L.ImageView()
     v.data, v.dtype = t.data_ptr(), codes[t.dtype]
     v.sn, v.sc, v.sh, v.sw = t.stride()
@@ -665,6 +665,26 @@ def fr_metrics(pred: torch.Tensor, ref: torch.Tensor, flags: int) -> torch.Tenso
         pv, rv = _image_view(pred), _image_view(ref)
         L.check(lib.dove_fr_metrics(C.byref(pv), C.byref(rv), N, Cc, H, W, flags, L.ptr(ws), ws.numel(), L.ptr(out), L.stream_ptr()),
                 "dove_fr_metrics")
+    return out
+
+
+def color_fix(content: torch.Tensor, style: torch.Tensor, mode: int, out: torch.Tensor, clamp: bool = True,
+              content_affine=(1.0, 0.0), style_affine=(1.0, 0.0)) -> torch.Tensor:
+    """content, style, out: [N,3,H,W] views (any strides, no copy; float32 / bfloat16 / uint8) -> ``out`` filled with the colour fix of
+    ``mode`` (L.COLORFIX_WAVELET / L.COLORFIX_ADAIN; csrc/colorfix.hip).  Each input is read as ``scale * raw + bias``."""
+    if content.dim() != 4 or content.shape[1] != 3 or content.shape != style.shape or content.shape != out.shape:
+        raise ValueError(f"color_fix: content {tuple(content.shape)}, style {tuple(style.shape)} and out {tuple(out.shape)} must be the "
+                         "same [N,3,H,W] shape")
+    if not (content.is_cuda and style.is_cuda and out.is_cuda) or content.device != style.device or content.device != out.device:
+        raise RuntimeError("color_fix needs content, style and out on the same HIP device (`cuda`); there is no CPU path")
+    N, _, H, W = content.shape
+    lib = L.load()
+    with torch.cuda.device(content.device):
+        ws = torch.empty(max(int(lib.dove_color_fix_workspace_bytes(mode, N, H, W)), 8), dtype=torch.uint8, device=content.device)
+        cv, sv, ov = _image_view(content), _image_view(style), _image_view(out)
+        L.check(lib.dove_color_fix(C.byref(cv), content_affine[0], content_affine[1], C.byref(sv), style_affine[0], style_affine[1],
+                                   N, H, W, mode, L.COLORFIX_CLAMP if clamp else 0, C.byref(ov), L.ptr(ws), ws.numel(), L.stream_ptr()),
+                "dove_color_fix")
     return out
 
 

@@ -42,11 +42,25 @@ def preprocess_frames_torch(frames_u8, pad_f, pad_h, pad_w, upscale, upscale_mod
     return (v / 255.0 * 2.0 - 1.0).permute(1, 0, 2, 3).contiguous().to(dtype)
 
 
-def postprocess_frames(video: torch.Tensor, pad_f: int, pad_h: int, pad_w: int, crop_scale: int = 4) -> torch.Tensor:
+def postprocess_frames(video: torch.Tensor, pad_f: int, pad_h: int, pad_w: int, crop_scale: int = 4, color_fix: str | None = None,
+                       source: torch.Tensor | None = None) -> torch.Tensor:
     """[1,3,F,H,W] in [0,1] -> [F',H',W',3] uint8 with the padding removed.  ``crop_scale`` is the reference's hard-coded 4
-    (ref :731 multiplies the LR pads by 4 regardless of --upscale)."""
+    (ref :731 multiplies the LR pads by 4 regardless of --upscale).
+
+    ``color_fix`` ('wavelet' / 'adain', dove_amd.colorfix) with ``source`` = the clip's upscaled input ([1,3,F,H,W] in [-1,1], what
+    ``preprocess_frames`` returned): the un-padded crop of ``video`` is colour-fixed against the same crop of ``source`` and comes out
+    as the uint8 frames directly.  The crop comes first, so the replicate border of the fix is the border of the frames returned - as if
+    the reference's color_fix_util had been run on the saved files."""
     _, _, F, H, W = video.shape
-    return ops.postprocess_u8(video[0].contiguous(), F - pad_f, H - pad_h * crop_scale, W - pad_w * crop_scale)
+    Fo, Ho, Wo = F - pad_f, H - pad_h * crop_scale, W - pad_w * crop_scale
+    if color_fix is None:
+        return ops.postprocess_u8(video[0].contiguous(), Fo, Ho, Wo)
+    if source is None or source.shape != video.shape:
+        raise ValueError(f"postprocess_frames(color_fix={color_fix!r}) needs source of the video's shape {tuple(video.shape)}")
+    from . import colorfix
+    content = video[0, :, :Fo, :Ho, :Wo].permute(1, 0, 2, 3)                 # [F',3,H',W'] views: nothing is copied
+    style = source[0, :, :Fo, :Ho, :Wo].permute(1, 0, 2, 3)
+    return colorfix.color_fix(content, style, color_fix, out_dtype=torch.uint8, style_affine=(0.5, 0.5))
 
 
 def load_frames(path: str) -> torch.Tensor:

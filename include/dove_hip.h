@@ -300,6 +300,24 @@ typedef struct dove_image_view {
 size_t dove_fr_metrics_workspace_bytes(int n, int h, int w);
 int dove_fr_metrics(const dove_image_view* pred, const dove_image_view* ref, int n, int channels, int h, int w, int flags, void* ws,
                     size_t ws_bytes, double* out, void* stream);
+/* Colour fix of restored frames against their upscaled input (the reference's finetune/scripts/color_fix_util.py):
+ * content (the SR result) keeps its detail and takes the colour of style (the upscaled low-quality input).  content, style and out are
+ * strided [n,3,h,w] views as above, every frame on its own; input dtypes DOVE_F32 / DOVE_BF16 / DOVE_U8 (read as value / 255), each
+ * followed by the affine  v = scale * raw + bias  (a [-1,1] clip is read as 0.5 x + 0.5 without a copy).
+ *   DOVE_COLORFIX_WAVELET: out = content + low5(style - content), low5 = five 3x3 [1,2,1]x[1,2,1]/16 blurs of dilation 1, 2, 4, 8, 16,
+ *     each on its replicate-padded input (= wavelet_reconstruction: (content - low5(content)) + low5(style)); any h, w >= 1.
+ *   DOVE_COLORFIX_ADAIN: out = (content - mean_c) / std_c * std_s + mean_s per frame and channel, std = sqrt(unbiased var + 1e-5)
+ *     (= adaptive_instance_normalization); needs h * w >= 2.
+ * out dtype DOVE_F32 / DOVE_BF16: the fp32 result (clamped to [0,1] with DOVE_COLORFIX_CLAMP); DOVE_U8: trunc(clamp(x,0,1) * 255), the rule
+ * of dove_postprocess_u8, so out may be the final [F,H,W,3] frames.  out may be the very view given as content or style (same pointer,
+ * strides and dtype), not a shifted or differently strided window onto one of them.  ws: device scratch of
+ * dove_color_fix_workspace_bytes(mode, n, h, w) bytes.  fp32 arithmetic (adain: fp64 statistics); two calls give identical bits. */
+#define DOVE_COLORFIX_WAVELET 1
+#define DOVE_COLORFIX_ADAIN 2
+#define DOVE_COLORFIX_CLAMP 1
+size_t dove_color_fix_workspace_bytes(int mode, int n, int h, int w);
+int dove_color_fix(const dove_image_view* content, float c_scale, float c_bias, const dove_image_view* style, float s_scale, float s_bias,
+                   int n, int h, int w, int mode, int flags, const dove_image_view* out, void* ws, size_t ws_bytes, void* stream);
 /* M = 1 linear with optional SiLU on the input (time_embedding MLP, norm*.linear modulation vectors) */
 int dove_gemv_bf16(const void* W, const float* bias, const float* x, int in_features, int out_features, int act_in,
                    float* y, void* stream);
