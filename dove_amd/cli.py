@@ -4,13 +4,14 @@ Every flag of the reference's parser (ref :507-554) is accepted: ``--input_dir -
 --lora_path --output_path --fps --dtype --seed --upscale_mode --upscale --noise_step --sr_noise_step --is_cpu_offload --is_vae_st
 --png_save --save_format --tile_size_hw --overlap_hw --chunk_len --overlap_t``; ``--color_fix {none,wavelet,adain}`` (not a flag of the reference's script: its
 ``finetune/scripts/color_fix_util.py`` on the GPU, dove_amd.colorfix) fixes every output frame against the clip's upscaled input.  ``--fps`` / ``--save_format`` describe the mp4
-container the reference writes with imageio - frame files carry neither, so they are accepted and reported; ``--is_cpu_offload``
+container the reference writes with imageio - frame files carry neither, so they are accepted and reported (with ``--y4m_save`` they are the
+frame rate and chroma layout of the ``<clip>.y4m`` written: YUV4MPEG2, dove_amd.y4m / dove_amd.stream); ``--is_cpu_offload``
 calls ``pipe.enable_sequential_cpu_offload()`` like the reference (a no-op with 288 GB of HBM); ``--eval_metrics`` knows ``psnr`` and
 ``ssim``, computed on the GPU (dove_amd.metrics) from the uint8 frames written to disk against ``--gt_dir/<clip>``, as the reference's
 ``eval_metrics.py`` scores the saved files; the per-clip values go to ``metrics_<names>.json`` in ``--output_path`` (the reference's
-structure, ref :755-776); the network metrics of pyiqa (lpips, dists, clipiqa, ...) are not provided; ``--dtype`` other than bfloat16 is refused.  Inputs are PNG folders
-or ``.npy`` clips (uint8 [F,H,W,3]) because H.264 decoding (decord) is outside the accelerated path; outputs are PNG
-folders or ``.npy``.  ``--random_init`` builds the CogVideoX1.5-5B architecture with synthetic weights (no checkpoint is
+structure, ref :755-776); the network metrics of pyiqa (lpips, dists, clipiqa, ...) are not provided; ``--dtype`` other than bfloat16 is refused.  Inputs are PNG folders,
+``.npy`` clips (uint8 [F,H,W,3]) or ``.y4m`` files because H.264 decoding (decord) is outside the accelerated path; outputs are PNG
+folders, ``.npy`` or ``.y4m`` (``--y4m_save``; streamed chunk by chunk when ``--chunk_len > 0``).  ``--random_init`` builds the CogVideoX1.5-5B architecture with synthetic weights (no checkpoint is
 available offline).  ``--eval_psnr_dir`` computes plain PSNR (10*log10(1/MSE), per-frame mean) on the CPU against ground-truth folders; with it,
 ``psnr`` in ``--eval_metrics`` is that value and the other metrics use ``--gt_dir`` (or those folders without ``--gt_dir``)."""
 from __future__ import annotations
@@ -21,60 +22,52 @@ import os
 import torch
 
 
-def main(argv=None):
-    ap = argparse.ArgumentParser(description="VSR using DOVE on MI355X (dove_amd)")
-    ap.add_argument("--input_dir", type=str, required=True)
-    ap.add_argument("--input_json", type=str, default=None, help="{clip name: prompt}; clips without an entry use the empty prompt (ref :590-594, :676)")
+def add_model_arguments(ap):
+    """The model and SR flags, shared with ``python -m dove_amd.stream``."""
     ap.add_argument("--model_path", type=str, default=None)
     ap.add_argument("--lora_path", type=str, default=None, help="LoRA weights to fuse into the transformer (ref :613-621)")
     ap.add_argument("--random_init", action="store_true")
-    ap.add_argument("--output_path", type=str, default="./results")
-    ap.add_argument("--gt_dir", type=str, default=None, help="ground-truth folders / .npy clips for --eval_metrics (ref :511)")
-    ap.add_argument("--eval_metrics", type=str, default="", help="any of 'psnr,ssim' (ref :513), on the GPU; the network metrics of pyiqa (lpips, ...) are not provided")
-    ap.add_argument("--fps", type=int, default=16, help="accepted like the reference (ref :521): frame files (PNG / .npy) carry no frame rate")
+    ap.add_argument("--fps", type=int, default=16, help="frame rate of the Y4M file (--y4m_save; ref :521); PNG / .npy frame files carry none")
     ap.add_argument("--dtype", type=str, default="bfloat16")
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--upscale_mode", type=str, default="bilinear", help="ref :527, :672; 'bilinear' is the fused HIP kernel, others run torch's interpolate")
     ap.add_argument("--upscale", type=int, default=4)
     ap.add_argument("--is_cpu_offload", action="store_true", help="ref :533, :637-641: enable_sequential_cpu_offload() (a no-op here)")
-    ap.add_argument("--save_format", type=str, default="yuv444p", help="accepted like the reference (ref :541): the pixel format of ITS mp4 writer")
+    ap.add_argument("--save_format", type=str, default="yuv444p",
+                    help="pixel format of the Y4M file (--y4m_save): yuv444p, yuv422p or yuv420p (ref :541); unused otherwise")
     ap.add_argument("--noise_step", type=int, default=0)
     ap.add_argument("--sr_noise_step", type=int, default=399)
     ap.add_argument("--is_vae_st", action="store_true")
-    ap.add_argument("--png_save", action="store_true")
     ap.add_argument("--tile_size_hw", type=int, nargs=2, default=(0, 0))
     ap.add_argument("--overlap_hw", type=int, nargs=2, default=(32, 32))
     ap.add_argument("--chunk_len", type=int, default=0)
     ap.add_argument("--overlap_t", type=int, default=8)
-    ap.add_argument("--eval_psnr_dir", type=str, default=None)
     ap.add_argument("--color_fix", type=str, default="none", choices=("none", "wavelet", "adain"),
                     help="colour-fix every output frame against the clip's upscaled input on the GPU (dove_amd.colorfix; the reference's "
                          "color_fix_util); saved and scored frames are the fixed ones")
+    ap.add_argument("--yuv_matrix", type=str, default="bt601", choices=("bt601", "bt709"),
+                    help="colour matrix of .y4m input and output (Y4M does not carry one; bt601 is what swscale assumes for RGB)")
+    ap.add_argument("--yuv_range", type=str, default=None, choices=("limited", "full"),
+                    help="range of .y4m output, and of .y4m input in place of its XCOLORRANGE tag (default: the tag / limited)")
     ap.add_argument("--num_layers", type=int, default=None, help="debug (with --random_init): fewer DiT layers than the 42 of CogVideoX1.5-5B")
     ap.add_argument("--prompt_embedding", type=str,
                     default="pretrained_models/prompt_embeddings/e3b0c44298fc1c149afbf4c8996fb92427ae41e4649b934ca495991b7852b855.safetensors")
-    args = ap.parse_args(argv)
+
+
+def check_dtype(args):
     if args.dtype != "bfloat16":
         raise ValueError(f"--dtype {args.dtype}: the HIP path computes in bfloat16 (the reference's default, ref :525); float16 / float32 "
                          "are not implemented (INTEGRATION.md, 'dtype')")
-    metrics = [m.strip().lower() for m in args.eval_metrics.split(",") if m.strip()]
-    if any(m not in ("psnr", "ssim") for m in metrics):
-        raise NotImplementedError(f"--eval_metrics {args.eval_metrics}: only 'psnr' and 'ssim' are computed here; the other pyiqa metrics "
-                                  "need network weights and are outside the path")
-    if metrics and not (args.gt_dir or args.eval_psnr_dir):
-        raise ValueError(f"--eval_metrics {args.eval_metrics} needs --gt_dir")
-    # with --eval_psnr_dir, PSNR stays on that flag's CPU path (against its folders, as before); the rest runs on the GPU against
-    # --gt_dir (or the --eval_psnr_dir folders when --gt_dir is not given)
-    gpu_metrics = [m for m in metrics if not (m == "psnr" and args.eval_psnr_dir)]
-    metrics_gt = args.gt_dir or args.eval_psnr_dir
 
+
+def build_pipe(args):
+    """The pipeline the flags of ``add_model_arguments`` describe, seeded and on the device -> (pipe, empty-prompt embedding)."""
     from safetensors.torch import load_file
 
-    from . import prepost, tiling
-    from .inference import process_video
     from .pipeline import CogVideoXPipeline
     from .scheduler import CogVideoXDPMScheduler
 
+    check_dtype(args)
     torch.manual_seed(args.seed)
     emb = load_file(args.prompt_embedding)["prompt_embedding"] if os.path.exists(args.prompt_embedding) else None
     if emb is None:
@@ -96,7 +89,90 @@ def main(argv=None):
         pipe.enable_sequential_cpu_offload()
     else:
         pipe.to("cuda")
-    if not args.png_save:
+    return pipe, emb
+
+
+def _y4m_writer(path, frames_shape, args, chroma):
+    from . import stream, y4m
+    Ho, Wo = stream.output_size(frames_shape[1], frames_shape[2], args.upscale)
+    return y4m.Y4MWriter(path, Wo, Ho, args.fps, chroma, args.yuv_range == "full")
+
+
+def _stream_clip(pipe, emb, args, name, prompt, frames, path, chroma, color_fix, need_frames):
+    """--y4m_save with --chunk_len > 0: the clip goes through ``stream.sr_stream`` chunk by chunk (one chunk of SR output on the device).
+    Returns the frames decoded from the file written when they are scored, else None."""
+    from . import prepost, stream, tiling
+    F, H, W, _ = frames.shape
+    pad_f, pad_h, pad_w = tiling.match_padding(F, H, W)
+    shape = (1, 3, F + pad_f, (H + pad_h) * args.upscale, (W + pad_w) * args.upscale)
+    items = tiling.plan(shape, args.chunk_len, args.overlap_t, tuple(args.tile_size_hw), tuple(args.overlap_hw))
+    print(f"Process video: {name} | Prompt: {prompt} | Frame: {shape[2]} (ori: {F}; pad: {pad_f}) | Target Resolution: "
+          f"{shape[3]}, {shape[4]} | Chunk Num: {len(items)}")
+    with _y4m_writer(path, frames.shape, args, chroma) as writer:
+        stream.sr_stream(pipe, stream.FrameSource(frames), writer, upscale=args.upscale, upscale_mode=args.upscale_mode,
+                         chunk_len=args.chunk_len, overlap_t=args.overlap_t, tile_size_hw=tuple(args.tile_size_hw),
+                         overlap_hw=tuple(args.overlap_hw), noise_step=args.noise_step, sr_noise_step=args.sr_noise_step, prompt=prompt,
+                         empty_prompt_embedding=emb, color_fix=color_fix, yuv_matrix=args.yuv_matrix, log=lambda msg: None)
+    return prepost.load_frames(path, yuv_matrix=args.yuv_matrix) if need_frames else None
+
+
+def _save_clip_y4m(out, video, pads, args, path, chroma, color_fix, need_frames):
+    """--y4m_save of a clip stitched in memory: the whole clip is converted at once (fused with the crop and the uint8 step unless a
+    colour fix runs first)."""
+    from . import prepost, yuv
+    pad_f, pad_h, pad_w = pads
+    fmt = yuv.YuvFormat(chroma, args.yuv_matrix, args.yuv_range or "limited")
+    _, _, F, H, W = out.shape
+    crop = (F - pad_f, H - pad_h * 4, W - pad_w * 4)
+    if color_fix:
+        payload = yuv.rgb_to_yuv(prepost.postprocess_frames(out, pad_f, pad_h, pad_w, color_fix=color_fix, source=video), fmt)
+    else:
+        payload = yuv.rgb_to_yuv(out, fmt, crop=crop)
+    from . import y4m
+    with y4m.Y4MWriter(path, crop[2], crop[1], args.fps, chroma, args.yuv_range == "full") as writer:
+        writer.write(payload.cpu())
+    return prepost.load_frames(path, yuv_matrix=args.yuv_matrix) if need_frames else None
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description="VSR using DOVE on MI355X (dove_amd)")
+    ap.add_argument("--input_dir", type=str, required=True)
+    ap.add_argument("--input_json", type=str, default=None, help="{clip name: prompt}; clips without an entry use the empty prompt (ref :590-594, :676)")
+    ap.add_argument("--output_path", type=str, default="./results")
+    ap.add_argument("--gt_dir", type=str, default=None, help="ground-truth folders / .npy / .y4m clips for --eval_metrics (ref :511)")
+    ap.add_argument("--eval_metrics", type=str, default="", help="any of 'psnr,ssim' (ref :513), on the GPU; the network metrics of pyiqa (lpips, ...) are not provided")
+    ap.add_argument("--png_save", action="store_true")
+    ap.add_argument("--y4m_save", action="store_true",
+                    help="write <clip>.y4m (YUV4MPEG2) with --fps and --save_format; with --chunk_len > 0 it is streamed chunk by chunk")
+    ap.add_argument("--eval_psnr_dir", type=str, default=None)
+    add_model_arguments(ap)
+    args = ap.parse_args(argv)
+    check_dtype(args)
+    metrics = [m.strip().lower() for m in args.eval_metrics.split(",") if m.strip()]
+    if any(m not in ("psnr", "ssim") for m in metrics):
+        raise NotImplementedError(f"--eval_metrics {args.eval_metrics}: only 'psnr' and 'ssim' are computed here; the other pyiqa metrics "
+                                  "need network weights and are outside the path")
+    if metrics and not (args.gt_dir or args.eval_psnr_dir):
+        raise ValueError(f"--eval_metrics {args.eval_metrics} needs --gt_dir")
+    # with --eval_psnr_dir, PSNR stays on that flag's CPU path (against its folders, as before); the rest runs on the GPU against
+    # --gt_dir (or the --eval_psnr_dir folders when --gt_dir is not given)
+    gpu_metrics = [m for m in metrics if not (m == "psnr" and args.eval_psnr_dir)]
+    metrics_gt = args.gt_dir or args.eval_psnr_dir
+    y4m_chroma = None
+    if args.y4m_save:
+        if args.png_save:
+            raise ValueError("--y4m_save and --png_save: choose one output form")
+        from . import yuv
+        y4m_chroma = yuv.save_format_to_chroma(args.save_format)      # refused only where a Y4M file is written
+
+    from . import prepost, tiling
+    from .inference import process_video
+
+    pipe, emb = build_pipe(args)
+    if args.y4m_save:
+        print(f"[dove_amd] clips are written as .y4m (YUV4MPEG2, {args.save_format}, {args.fps} fps, {args.yuv_matrix} / "
+              f"{args.yuv_range or 'limited'}); --eval_metrics score the frames decoded from that file")
+    elif not args.png_save:
         print(f"[dove_amd] clips are written as .npy frame arrays (uint8 [F,H,W,3]); --fps {args.fps} / --save_format {args.save_format} "
               "apply to the reference's mp4 writer only")
     if args.is_vae_st:
@@ -109,9 +185,11 @@ def main(argv=None):
     overlap_t = args.overlap_t if args.chunk_len > 0 else 0
     os.makedirs(args.output_path, exist_ok=True)
     names = sorted(n for n in os.listdir(args.input_dir)
-                   if n.lower().endswith(".npy") or os.path.isdir(os.path.join(args.input_dir, n)))
+                   if n.lower().endswith((".npy", ".y4m")) or os.path.isdir(os.path.join(args.input_dir, n)))
     if not names:
-        raise ValueError(f"No clips (.npy or PNG folders) found in {args.input_dir}")
+        raise ValueError(f"No clips (.npy, .y4m or PNG folders) found in {args.input_dir}")
+    yuv_in = {"yuv_matrix": args.yuv_matrix, "yuv_range": args.yuv_range}    # how .y4m clips (input and ground truth) are read
+    need_frames = bool(metrics or args.eval_psnr_dir)
     prompts = {}
     if args.input_json is not None:
         import json
@@ -121,37 +199,46 @@ def main(argv=None):
     scores = {m: [] for m in metrics}                                     # per clip, in clip order (ref :647-656, :755-776)
     for name in names:
         prompt = prompts.get(name, "")
-        frames = prepost.load_frames(os.path.join(args.input_dir, name))
-        video, pad_f, pad_h, pad_w, orig = prepost.preprocess_frames(frames, args.upscale, upscale_mode=args.upscale_mode)
-        items = tiling.plan(video.shape, args.chunk_len, overlap_t, tuple(args.tile_size_hw), tuple(args.overlap_hw))
-        out = torch.zeros(video.shape, dtype=torch.bfloat16, device=video.device)
-        wc = torch.zeros(video.shape, dtype=torch.int32, device=video.device)
-        print(f"Process video: {name} | Prompt: {prompt} | Frame: {video.shape[2]} (ori: {orig[0]}; pad: {pad_f}) | Target Resolution: "
-              f"{video.shape[3]}, {video.shape[4]} | Chunk Num: {len(items)}")
-        for (t0, t1, h0, h1, w0, w1), region in items:
-            piece = process_video(pipe, video[:, :, t0:t1, h0:h1, w0:w1], prompt=prompt, noise_step=args.noise_step,
-                                  sr_noise_step=args.sr_noise_step, empty_prompt_embedding=emb)
-            tiling.stitch(out, wc, piece, region)
-        tiling.check_coverage(wc)
-        if color_fix:
-            frames_out = prepost.postprocess_frames(out, pad_f, pad_h, pad_w, color_fix=color_fix, source=video)
+        frames = prepost.load_frames(os.path.join(args.input_dir, name), **yuv_in)
+        stem = name[:-4] if name.lower().endswith((".npy", ".y4m")) else name
+        if args.y4m_save and args.chunk_len > 0:
+            frames_out = _stream_clip(pipe, emb, args, name, prompt, frames, os.path.join(args.output_path, stem + ".y4m"), y4m_chroma,
+                                      color_fix, need_frames)
         else:
-            frames_out = prepost.postprocess_frames(out, pad_f, pad_h, pad_w)   # the reference crops pad*4 (ref :731)
-        stem = name[:-4] if name.lower().endswith(".npy") else name
-        if args.png_save:
+            video, pad_f, pad_h, pad_w, orig = prepost.preprocess_frames(frames, args.upscale, upscale_mode=args.upscale_mode)
+            items = tiling.plan(video.shape, args.chunk_len, overlap_t, tuple(args.tile_size_hw), tuple(args.overlap_hw))
+            out = torch.zeros(video.shape, dtype=torch.bfloat16, device=video.device)
+            wc = torch.zeros(video.shape, dtype=torch.int32, device=video.device)
+            print(f"Process video: {name} | Prompt: {prompt} | Frame: {video.shape[2]} (ori: {orig[0]}; pad: {pad_f}) | Target Resolution: "
+                  f"{video.shape[3]}, {video.shape[4]} | Chunk Num: {len(items)}")
+            for (t0, t1, h0, h1, w0, w1), region in items:
+                piece = process_video(pipe, video[:, :, t0:t1, h0:h1, w0:w1], prompt=prompt, noise_step=args.noise_step,
+                                      sr_noise_step=args.sr_noise_step, empty_prompt_embedding=emb)
+                tiling.stitch(out, wc, piece, region)
+            tiling.check_coverage(wc)
+            if args.y4m_save:
+                frames_out = _save_clip_y4m(out, video, (pad_f, pad_h, pad_w), args, os.path.join(args.output_path, stem + ".y4m"),
+                                            y4m_chroma, color_fix, need_frames)
+            elif color_fix:
+                frames_out = prepost.postprocess_frames(out, pad_f, pad_h, pad_w, color_fix=color_fix, source=video)
+            else:
+                frames_out = prepost.postprocess_frames(out, pad_f, pad_h, pad_w)   # the reference crops pad*4 (ref :731)
+        if args.y4m_save:
+            pass
+        elif args.png_save:
             prepost.save_frames_as_png(frames_out, os.path.join(args.output_path, stem))
         else:
             import numpy as np
             np.save(os.path.join(args.output_path, stem + ".npy"), frames_out.cpu().numpy())
         if args.eval_psnr_dir:
-            gt = prepost.load_frames(os.path.join(args.eval_psnr_dir, name)).float() / 255
+            gt = prepost.load_frames(os.path.join(args.eval_psnr_dir, name), **yuv_in).float() / 255
             pr = frames_out.cpu().float() / 255
             mse = ((gt - pr) ** 2).flatten(1).mean(1)
             psnrs[name] = float((10 * torch.log10(1.0 / (mse + 1e-8))).mean())
             print(f"[{name}] PSNR={psnrs[name]:.4f}")
         if gpu_metrics:
             from .metrics import clip_metrics
-            gt = prepost.load_frames(os.path.join(metrics_gt, name))
+            gt = prepost.load_frames(os.path.join(metrics_gt, name), **yuv_in)
             vals = clip_metrics(frames_out, gt, gpu_metrics)
             for m in gpu_metrics:
                 print(f"[{name}] {m.upper()}={vals[m]:.4f}")

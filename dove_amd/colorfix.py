@@ -107,7 +107,7 @@ def fix_clip(pred_u8: torch.Tensor, source_u8: torch.Tensor, mode: str) -> torch
 
 
 def save_sequence(frames_u8: torch.Tensor, like: str, out_root: str) -> str:
-    """Write the fixed frames in the form of the prediction at ``like``: a PNG folder, one image, or an ``.npy`` clip."""
+    """Write the fixed frames in the form of the prediction at ``like``: a PNG folder, one image, an ``.npy`` clip or a ``.y4m`` file."""
     from . import prepost
     base = os.path.basename(like.rstrip(os.sep))
     path = os.path.join(out_root, base)
@@ -116,6 +116,13 @@ def save_sequence(frames_u8: torch.Tensor, like: str, out_root: str) -> str:
     elif like.lower().endswith(".npy"):
         import numpy as np
         np.save(path, frames_u8.cpu().numpy())
+    elif like.lower().endswith(".y4m"):                       # the prediction's own frame rate, chroma layout and range (bt601)
+        from . import y4m, yuv
+        with y4m.Y4MReader(like) as rd:
+            fps, chroma, full = rd.fps, rd.chroma, rd.full_range
+        payload = yuv.rgb_to_yuv(frames_u8.cuda(), yuv.YuvFormat(chroma, "bt601", "full" if full else "limited"))
+        with y4m.Y4MWriter(path, frames_u8.shape[2], frames_u8.shape[1], fps, chroma, full) as wr:
+            wr.write(payload.cpu())
     else:
         from PIL import Image
         path = os.path.splitext(path)[0] + ".png"

@@ -4,7 +4,8 @@ SSIM computed on the GPU (dove_amd.metrics, csrc/metrics.hip).
 Same flags (``--gt --pred --out --metrics --batch_mode --crop --test_y_channel --is_center``), the same pairing of predictions and
 ground truth by ``os.path.splitext`` stem, the same per-clip steps (match_resolution, crop_border, rgb_to_y), the same printout and the
 same JSON (``metrics_<names>.json``: per_sample {clip: {metric: round(value, 4)}}, average of the rounded values, count).
-Inputs are PNG/JPG folders, single images and ``.npy`` clips (uint8 [F,H,W,3]); mp4 decoding is not provided.  ``--metrics``
+Inputs are PNG/JPG folders, single images, ``.npy`` clips (uint8 [F,H,W,3]) and ``.y4m`` files (YUV4MPEG2, read as bt601 with the
+stream's range tag; dove_amd.y4m); mp4 decoding is not provided.  ``--metrics``
 defaults to ``psnr,ssim`` (the reference's default also lists clipiqa, which needs network weights); a metric other than psnr / ssim
 fails to initialise with a message, as a pyiqa metric that cannot be created does in the reference."""
 from __future__ import annotations
@@ -23,7 +24,7 @@ FR_METRICS = ["psnr", "ssim", "lpips", "dists"]          # eval_metrics.py's ful
 
 
 def load_sequence(path: str) -> torch.Tensor:
-    """A PNG/JPG folder, a single image (one frame) or an ``.npy`` clip -> uint8 [F,H,W,3] (host)."""
+    """A PNG/JPG folder, a single image (one frame), an ``.npy`` clip or a ``.y4m`` file -> uint8 [F,H,W,3] (host)."""
     if os.path.isfile(path) and path.lower().endswith((".png", ".jpg", ".jpeg")):
         from PIL import Image
         return torch.from_numpy(np.asarray(Image.open(path).convert("RGB")).copy())[None]

@@ -14,6 +14,8 @@ _lib = None
 F32, BF16, U8 = 0, 1, 2
 METRIC_PSNR, METRIC_SSIM, METRIC_RGB_TO_Y = 1, 2, 4           # dove_fr_metrics flags
 COLORFIX_WAVELET, COLORFIX_ADAIN, COLORFIX_CLAMP = 1, 2, 1    # dove_color_fix modes / flag
+YUV_444, YUV_422, YUV_420, YUV_MONO = 0, 1, 2, 3              # dove_yuv_format.chroma
+YUV_SITING_LEFT, YUV_SITING_CENTRE = 0, 1                     # dove_yuv_format.siting_h
 
 
 class ConvDesc(C.Structure):
@@ -53,6 +55,11 @@ class ImageView(C.Structure):
     """dove_image_view (include/dove_hip.h): a strided 4-D view, element (n, c, y, x) at data + n*sn + c*sc + y*sh + x*sw elements."""
     _fields_ = [("data", C.c_void_p), ("dtype", C.c_int), ("reserved", C.c_int),
                 ("sn", C.c_longlong), ("sc", C.c_longlong), ("sh", C.c_longlong), ("sw", C.c_longlong)]
+
+
+class YuvFormat(C.Structure):
+    """dove_yuv_format (include/dove_hip.h): a fixed-point 3x3 matrix (rint(c * 65536)), the offsets, the chroma layout and siting."""
+    _fields_ = [("coef", C.c_int * 9), ("offset", C.c_int * 3), ("chroma", C.c_int), ("siting_h", C.c_int)]
 
 
 class DitAux(C.Structure):
@@ -130,6 +137,8 @@ SIGNATURES = {
     "dove_fr_metrics": [C.POINTER(ImageView), C.POINTER(ImageView), _I, _I, _I, _I, _I, _VP, C.c_size_t, _VP, _VP],
     "dove_color_fix": [C.POINTER(ImageView), _F, _F, C.POINTER(ImageView), _F, _F, _I, _I, _I, _I, _I, C.POINTER(ImageView), _VP,
                        C.c_size_t, _VP],
+    "dove_rgb_to_yuv_u8": [C.POINTER(ImageView), _I, _I, _I, C.POINTER(YuvFormat), _VP, _VP],
+    "dove_yuv_to_rgb_u8": [_VP, _I, _I, _I, C.POINTER(YuvFormat), _VP, _VP],
 }
 PLAIN = {"dove_last_error": (C.c_char_p, []), "dove_abi_version": (C.c_int, []), "dove_comm_destroy": (None, [C.c_void_p]),
          "dove_conv_gn_partial_rows": (C.c_longlong, [C.POINTER(ConvDesc)]),
@@ -145,7 +154,8 @@ PLAIN = {"dove_last_error": (C.c_char_p, []), "dove_abi_version": (C.c_int, []),
          "dove_workspace_bytes": (C.c_size_t, [_VP, _I, _I, _I]),
          "dove_workspace_high_water": (C.c_size_t, [_VP]),
          "dove_fr_metrics_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
-         "dove_color_fix_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I])}
+         "dove_color_fix_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I]),
+         "dove_yuv_frame_bytes": (C.c_size_t, [_I, _I, _I])}
 
 
 def kernel_source_sha256() -> str:

@@ -688,6 +688,40 @@ def color_fix(content: torch.Tensor, style: torch.Tensor, mode: int, out: torch.
     return out
 
 
+def yuv_frame_bytes(h: int, w: int, chroma: int) -> int:
+    return int(L.load().dove_yuv_frame_bytes(h, w, chroma))
+
+
+def rgb_to_yuv_u8(rgb: torch.Tensor, fmt: L.YuvFormat) -> torch.Tensor:
+    """rgb: a [N,3,H,W] view (any strides, no copy; uint8, or float32 / bfloat16 in [0,1]) -> [N, frame_bytes] uint8 Y4M frame payloads
+    (Y, U, V planes; csrc/yuv.hip).  ``fmt`` carries the forward matrix."""
+    if rgb.dim() != 4 or rgb.shape[1] != 3:
+        raise ValueError(f"rgb_to_yuv_u8: rgb {tuple(rgb.shape)} must be a [N,3,H,W] view")
+    if not rgb.is_cuda:
+        raise RuntimeError("rgb_to_yuv_u8 needs its input on the HIP device (`cuda`); there is no CPU path")
+    N, _, H, W = rgb.shape
+    lib = L.load()
+    with torch.cuda.device(rgb.device):
+        out = torch.empty(N, int(lib.dove_yuv_frame_bytes(H, W, fmt.chroma)), dtype=torch.uint8, device=rgb.device)
+        v = _image_view(rgb)
+        L.check(lib.dove_rgb_to_yuv_u8(C.byref(v), N, H, W, C.byref(fmt), L.ptr(out), L.stream_ptr()), "dove_rgb_to_yuv_u8")
+    return out
+
+
+def yuv_to_rgb_u8(payload: torch.Tensor, h: int, w: int, fmt: L.YuvFormat) -> torch.Tensor:
+    """payload [N, frame_bytes] uint8 (contiguous Y4M frame payloads) -> [N,h,w,3] uint8 frames (csrc/yuv.hip).  ``fmt`` carries the inverse
+    matrix."""
+    L.require_cuda(payload)
+    lib = L.load()
+    fb = int(lib.dove_yuv_frame_bytes(h, w, fmt.chroma))
+    if payload.dtype != torch.uint8 or payload.dim() != 2 or payload.shape[1] != fb or fb == 0:
+        raise ValueError(f"yuv_to_rgb_u8: payload {tuple(payload.shape)} {payload.dtype} is not uint8 [N, {fb}] for {w}x{h}")
+    N = payload.shape[0]
+    out = torch.empty(N, h, w, 3, dtype=torch.uint8, device=payload.device)
+    L.check(lib.dove_yuv_to_rgb_u8(L.ptr(payload), N, h, w, C.byref(fmt), L.ptr(out), L.stream_ptr()), "dove_yuv_to_rgb_u8")
+    return out
+
+
 # ---- MXFP8 linears (BASELINE configs[4]; csrc/mxfp8.hip) ------------------------------------------------------------------
 @dataclass
 class PackedMx:

@@ -3,7 +3,8 @@
 Mirrors /root/reference/inference_script.py: ``preprocess_video_match`` padding (:192-235), the bilinear upscale and
 [-1,1] normalisation (:670-679), ``remove_padding_and_extra_frames`` (:238-246, called with the reference's hard-coded
 ``pad*4`` at :731) and the uint8 conversion of the savers (:124).  Video decoding (decord/H.264) stays outside: clips
-come in as uint8 arrays ([F,H,W,3] ``.npy``) or PNG folders."""
+come in as uint8 arrays ([F,H,W,3] ``.npy``), PNG folders or YUV4MPEG2 files (``.y4m``, the codec-free container of
+``ffmpeg -f yuv4mpegpipe``; dove_amd.y4m, dove_amd.yuv)."""
 from __future__ import annotations
 
 import os
@@ -63,9 +64,32 @@ def postprocess_frames(video: torch.Tensor, pad_f: int, pad_h: int, pad_w: int, 
     return colorfix.color_fix(content, style, color_fix, out_dtype=torch.uint8, style_affine=(0.5, 0.5))
 
 
-def load_frames(path: str) -> torch.Tensor:
-    """``.npy`` ([F,H,W,3] uint8) or a folder of PNG/JPG frames -> uint8 tensor [F,H,W,3]."""
+def load_y4m(path, yuv_matrix: str = "bt601", yuv_range: str | None = None, block: int = 64) -> torch.Tensor:
+    """A YUV4MPEG2 file (or binary file object) -> host uint8 [F,H,W,3]: ``y4m.Y4MReader`` -> ``yuv.yuv_to_rgb`` on the GPU, ``block``
+    frames at a time.  Y4M carries no colour matrix (``yuv_matrix``); ``yuv_range`` overrides the stream's XCOLORRANGE tag."""
+    from . import y4m, yuv
+    if not torch.cuda.is_available():
+        raise RuntimeError("a .y4m clip is converted to RGB on the GPU (csrc/yuv.hip); no HIP device is visible")
+    out = []
+    with y4m.Y4MReader(path) as rd:
+        fmt = yuv.format_of_reader(rd, yuv_matrix, yuv_range)
+        while True:
+            payload = rd.read(block)
+            if payload.shape[0]:
+                out.append(yuv.yuv_to_rgb(payload.cuda(), rd.height, rd.width, fmt).cpu())
+            if payload.shape[0] < block:
+                break
+    if not out:
+        raise ValueError(f"no frames in {path}")
+    return torch.cat(out)
+
+
+def load_frames(path: str, yuv_matrix: str = "bt601", yuv_range: str | None = None) -> torch.Tensor:
+    """``.npy`` ([F,H,W,3] uint8), a ``.y4m`` file (YUV4MPEG2; converted on the GPU) or a folder of PNG/JPG frames -> uint8 tensor
+    [F,H,W,3] on the host."""
     import numpy as np
+    if os.path.isfile(path) and path.lower().endswith(".y4m"):
+        return load_y4m(path, yuv_matrix, yuv_range)
     if os.path.isdir(path):
         from PIL import Image
         names = sorted(n for n in os.listdir(path) if n.lower().endswith((".png", ".jpg", ".jpeg")))
@@ -76,7 +100,7 @@ def load_frames(path: str) -> torch.Tensor:
         arr = np.load(path)
     else:
         raise ValueError(f"unsupported input {path}: H.264 decoding (decord) is outside the accelerated path; "
-                         "convert the clip to a PNG folder or an .npy array")
+                         "convert the clip to a PNG folder, an .npy array or a .y4m file (ffmpeg -i clip -pix_fmt yuv420p -f yuv4mpegpipe clip.y4m)")
     if arr.dtype != np.uint8 or arr.ndim != 4 or arr.shape[3] != 3:
         raise ValueError(f"expected uint8 [F,H,W,3], got {arr.dtype} {arr.shape}")
     return torch.from_numpy(arr.copy())

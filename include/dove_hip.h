@@ -318,6 +318,34 @@ int dove_fr_metrics(const dove_image_view* pred, const dove_image_view* ref, int
 size_t dove_color_fix_workspace_bytes(int mode, int n, int h, int w);
 int dove_color_fix(const dove_image_view* content, float c_scale, float c_bias, const dove_image_view* style, float s_scale, float s_bias,
                    int n, int h, int w, int mode, int flags, const dove_image_view* out, void* ws, size_t ws_bytes, void* stream);
+/* 8-bit RGB <-> planar YUV for YUV4MPEG2 video I/O (tests/yuv_ref.py is the bit-exact definition).  Integer fixed
+ * point with 16 fractional bits: the caller passes the 3x3 matrix as rint(c * 65536) and the offsets (16 or 0, 128, 128); a result is
+ * rounded once (+ half before the final arithmetic shift) and clamped to 0..255.  A frame payload is the Y plane [h,w], then U, then V
+ * (DOVE_YUV_444: [h,w]; DOVE_YUV_422: [h, ceil(w/2)]; DOVE_YUV_420: [ceil(h/2), ceil(w/2)]; DOVE_YUV_MONO: none), contiguous and
+ * dove_yuv_frame_bytes long (0 for a bad argument) - what follows "FRAME\n" in a Y4M stream.
+ * rgb_to_yuv: rgb is a strided [n,3,h,w] view as above (u8 frames [F,H,W,3], or [3,F,H,W] f32 / bf16 decoder output in [0,1] and crops
+ *   of it); a float sample is first quantised as dove_postprocess_u8 does, trunc(clamp(x*255,0,255)).  offset[] is added to Y, U, V.
+ *   422 chroma: [1 2 1]/4 at even x (left co-sited); 420: mean of the 2x2 block (centre-sited, C420jpeg); edges replicate; the filter
+ *   runs on the un-rounded products.  out: n payloads.
+ * yuv_to_rgb: yuv holds n payloads; offset[] is subtracted from Y, U, V; out is [n,h,w,3] u8.  Chroma is upsampled bilinearly with
+ *   integer weights (sum 4 per axis, neighbours clamped) and enters the matrix product still scaled: 420 vertical 3:1 towards the nearer
+ *   sample; 420 horizontal 3:1 when siting_h is DOVE_YUV_SITING_CENTRE (C420jpeg), else 4:0 at even x and 2:2 at odd x (C420mpeg2,
+ *   C420paldv), as 422 always is.  DOVE_YUV_MONO gives grey RGB. */
+#define DOVE_YUV_444 0
+#define DOVE_YUV_422 1
+#define DOVE_YUV_420 2
+#define DOVE_YUV_MONO 3
+#define DOVE_YUV_SITING_LEFT 0
+#define DOVE_YUV_SITING_CENTRE 1
+typedef struct dove_yuv_format {
+  int coef[9];   /* row-major 3x3: rows Y, U, V (forward) or R, G, B (inverse) */
+  int offset[3];
+  int chroma;    /* DOVE_YUV_444 / 422 / 420 / MONO */
+  int siting_h;  /* DOVE_YUV_SITING_*: read by yuv_to_rgb for DOVE_YUV_420 only */
+} dove_yuv_format;
+size_t dove_yuv_frame_bytes(int h, int w, int chroma);
+int dove_rgb_to_yuv_u8(const dove_image_view* rgb, int n, int h, int w, const dove_yuv_format* fmt, void* out, void* stream);
+int dove_yuv_to_rgb_u8(const void* yuv, int n, int h, int w, const dove_yuv_format* fmt, void* out, void* stream);
 /* M = 1 linear with optional SiLU on the input (time_embedding MLP, norm*.linear modulation vectors) */
 int dove_gemv_bf16(const void* W, const float* bias, const float* x, int in_features, int out_features, int act_in,
                    float* y, void* stream);
