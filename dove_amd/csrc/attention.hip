@@ -2,7 +2,8 @@
 // RUNNING-MAXIMUM kernel.  Heads the caller hands a finite score bound for (norm2) run on the software-pipelined no-shift kernel of
 // attention_pipe.hip first (round 5: bound <= 40; round 6: every finite bound, the row sums checked in that kernel's epilogue); this kernel
 // keeps the heads that one marked NaN, the heads whose bound was not finite - and every head when no bound is given - and exits at once for a
-// head the other kernel finished.  Its own constant-shift loop (below) is what the timing library's DOVE_ATTN_PIPE=0 A/B runs.
+// head the other kernel finished.  Its own constant-shift loop (below) runs only for a caller that gives a bound and skip_bounded == 0,
+// which this library's entry point never does (rounds 3-4 ran the bounded heads on it).
 //   head_dim 64, bf16 MFMA 32x32x16, fp32 online softmax, non-causal, no mask, N not a tile multiple.
 // Replaces F.scaled_dot_product_attention inside diffusers' CogVideoXAttnProcessor2_0, reached from
 // /root/reference/inference_script.py:483-489.
@@ -58,7 +59,9 @@ __device__ __forceinline__ f32x16 mfma_c_in(bf16x8 a, bf16x8 b, const f32x16& c)
   return d;
 }
 
-// NW = waves per workgroup: NW x 32 queries share every K / V^T tile (waves 0-3 stage them).
+// NW = waves per workgroup: NW x 32 queries share every K / V^T tile (waves 0-3 stage them).  The library instantiates <4, true, false> only:
+// 8 waves sharing a tile measured within noise of 4 (0 / +1.7 % on two boxes), 6 waves -13 %; the 2-D grid (XCD = false) and FIXED (a
+// compile-time constant shift) were experiments.  The entry point that launched those variants left with the timing library (git history).
 // XCD: 1-D grid of heads x query-blocks, remapped so that each XCD (= blockIdx % 8, its own L2) walks a CONTIGUOUS range of the
 // head-major tile list: the ~64 workgroups an XCD runs at a time then belong to one or two heads and stream the same K / V^T tiles
 // through one L2, instead of every XCD streaming every head (the 2-D grid puts consecutive query blocks of a head on 8 XCDs).
@@ -110,7 +113,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_kernel(const bf16_t* __re
   // 2^-2b, and 2^-80 keeps P, l and the P V products far inside the NORMAL fp32 / bf16 range (60, the first cutoff, left 2^-120 - six binades
   // above the denormals, less than |v| can take away; LayerNorm'd q / k give b ~ 12).
   bool fixed = FIXED;
-  if (bound && !skip_bounded) {       // (timing library only: DOVE_ATTN_PIPE=0 - the constant-shift loop of rounds 3-4 for the A/B)
+  if (bound && !skip_bounded) {       // (never taken from dove_attention_fwd_bf16: the constant-shift loop of rounds 3-4)
     const float b = FIXED ? bound[h] : 1.01f * sqrtf(bound[2 * h] * bound[2 * h + 1]);   // [head][q, k]: max squared row norms
     fixed = FIXED || b <= 40.0f;      // NaN compares false: the running maximum
     if (fixed) {
@@ -290,30 +293,21 @@ extern "C" int dove_attention_fwd_bf16(const void* Qh, const void* Kh, const voi
   DOVE_CHECK_ARG(Npad * 128 < (1ll << 31), "attention_fwd: sequence too long for 31-bit buffer offsets");
   DOVE_CHECK_ARG(ldo >= (long long)heads * 64 && ldo % 4 == 0, "attention_fwd: bad ldo");
   constexpr int LDS = 4 * 16384;
-  constexpr int NW = 4;                          // tools/archive/attn_nw.py: 8 waves sharing a tile = 4 within noise (0 / +1.7 % on two boxes), 6 waves -13 %
+  constexpr int NW = 4;
   static PerDeviceOnce attr_set;
   if (auto once_ = attr_set.guard()) {
     (void)hipFuncSetAttribute((const void*)(attn_fwd_kernel<NW, true>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
   }
   const int qblocks = (int)((Npad + NW * 32 - 1) / (NW * 32));
   DOVE_CHECK_ARG((long long)qblocks * heads < (1ll << 31), "attention_fwd: grid too large");
-#ifdef DOVE_TIMING_BUILD
-  { const char* e = getenv("DOVE_ATTN_BOUND"); if (e && atoi(e) == 0) norm2 = nullptr; }   // tools/e2e_env_ab.py: running maximum vs bound
-#endif
   // With a score bound per head (norm2) every head whose bound is finite runs on the software-pipelined kernel (attention_pipe.hip: one wave
   // per SIMD, no shift), which marks norm2[2 h] NaN for a head whose row sums left its safe window; those, the heads with a non-finite bound -
   // and every head when no bound is given - run here on the running maximum, AFTER the other kernel on the same stream: the final contents of
   // every output row come from exactly one of them, and norm2 says which (dove_attention_head_paths).
-  int skip_bounded = 0;
+  const int skip_bounded = norm2 ? 1 : 0;
   if (norm2) {
-    skip_bounded = 1;
-#ifdef DOVE_TIMING_BUILD
-    { const char* e = getenv("DOVE_ATTN_PIPE"); if (e && atoi(e) == 0) skip_bounded = 0; }   // tools/e2e_env_ab.py: the bounded heads on this kernel's constant-shift loop
-#endif
-    if (skip_bounded) {
-      const int rc = dove_attention_pipe_launch(Qh, Kh, Vt, O, N, Npad, heads, ldo, norm2, stream);
-      if (rc) return rc;
-    }
+    const int rc = dove_attention_pipe_launch(Qh, Kh, Vt, O, N, Npad, heads, ldo, norm2, stream);
+    if (rc) return rc;
   }
   hipLaunchKernelGGL((attn_fwd_kernel<NW, true>), dim3((unsigned)(qblocks * heads)), dim3(NW * 64), LDS, (hipStream_t)stream, (const bf16_t*)Qh,
                      (const bf16_t*)Kh, (const bf16_t*)Vt, (bf16_t*)O, N, Npad, ldo, qblocks, norm2, skip_bounded);
@@ -327,42 +321,3 @@ extern "C" int dove_attention_head_paths(const float* norm2_host, int heads, int
   return DOVE_OK;
 }
 extern "C" const char* dove_attention_path_name(int path) { return path == 1 ? "attn_pipe_kernel" : path == 0 ? "attn_fwd_kernel" : ""; }
-
-#ifdef DOVE_TIMING_BUILD
-// tools/archive/attn_nw.py: the same kernel with 4 / 6 / 8 waves per workgroup (occupancy 2 / 3 / 4 waves per SIMD by LDS) on the 2-D grid, and
-// nw = 14: 4 waves with the XCD-contiguous 1-D grid (the product mapping), within one run
-extern "C" int dove_attention_fwd_bf16_nw(const void* Qh, const void* Kh, const void* Vt, void* O, long long N, long long Npad, int heads,
-                                          long long ldo, int nw, void* stream) {
-  constexpr int LDS = 4 * 16384;
-  static PerDeviceOnce attr_set;
-  if (auto once_ = attr_set.guard()) {
-    (void)hipFuncSetAttribute((const void*)(attn_fwd_kernel<4, false>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    (void)hipFuncSetAttribute((const void*)(attn_fwd_kernel<6, false>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    (void)hipFuncSetAttribute((const void*)(attn_fwd_kernel<8, false>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    (void)hipFuncSetAttribute((const void*)(attn_fwd_kernel<4, true>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    (void)hipFuncSetAttribute((const void*)(attn_fwd_kernel<4, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-  }
-  static float* fixed_bound = nullptr;           // experiment (nw = 44 / 54): a constant score bound for every head
-  if (!fixed_bound) {
-    float hb[256];
-    for (int i = 0; i < 256; ++i) hb[i] = 24.0f;   // 44: the bound itself; 54 (run-time path): sqrt(24 * 24) * 1.01
-    (void)hipMalloc((void**)&fixed_bound, sizeof(hb));
-    (void)hipMemcpy(fixed_bound, hb, sizeof(hb), hipMemcpyHostToDevice);
-  }
-  const int w = nw >= 14 ? 4 : nw;
-  const int qblocks = (int)((Npad + w * 32 - 1) / (w * 32));
-  dim3 grid((unsigned)qblocks, heads);
-  hipStream_t s = (hipStream_t)stream;
-#define ATTN_ARGS (const bf16_t*)Qh, (const bf16_t*)Kh, (const bf16_t*)Vt, (bf16_t*)O, N, Npad, ldo, qblocks
-  if (nw == 4) hipLaunchKernelGGL((attn_fwd_kernel<4, false>), grid, dim3(256), LDS, s, ATTN_ARGS);
-  else if (nw == 6) hipLaunchKernelGGL((attn_fwd_kernel<6, false>), grid, dim3(384), LDS, s, ATTN_ARGS);
-  else if (nw == 8) hipLaunchKernelGGL((attn_fwd_kernel<8, false>), grid, dim3(512), LDS, s, ATTN_ARGS);
-  else if (nw == 14) hipLaunchKernelGGL((attn_fwd_kernel<4, true>), dim3((unsigned)(qblocks * heads)), dim3(256), LDS, s, ATTN_ARGS);
-  else if (nw == 44) hipLaunchKernelGGL((attn_fwd_kernel<4, true, true>), dim3((unsigned)(qblocks * heads)), dim3(256), LDS, s, ATTN_ARGS, fixed_bound);
-  else if (nw == 54) hipLaunchKernelGGL((attn_fwd_kernel<4, true>), dim3((unsigned)(qblocks * heads)), dim3(256), LDS, s, ATTN_ARGS, fixed_bound);
-  else return -1;
-#undef ATTN_ARGS
-  DOVE_CHECK_LAUNCH("dove_attention_fwd_bf16_nw");
-  return DOVE_OK;
-}
-#endif

@@ -382,20 +382,3 @@ extern "C" int dove_attention_fwd_mxfp8(const void* Q8, const void* K8, const vo
   DOVE_CHECK_LAUNCH("dove_attention_fwd_mxfp8");
   return DOVE_OK;
 }
-
-#ifdef DOVE_TIMING_BUILD
-extern "C" int dove_attention_fwd_mxfp8_nw(const void* Q8, const void* K8, const void* V8t, const void* Vs, void* O, long long N, long long Npad,
-                                           int heads, long long ldo, int nw, void* stream) {
-  constexpr int LDS = 4 * 8192;
-  const int w = nw == 14 ? 4 : nw;
-  const int qb = (int)((Npad + w * 32 - 1) / (w * 32));
-  dim3 grid((unsigned)qb, heads);
-#define MXL(W, G, QB) hipLaunchKernelGGL(attn_fwd_mx_kernel<W>, G, dim3(W * 64), LDS, (hipStream_t)stream, (const unsigned char*)Q8, (const unsigned char*)K8, \
-                                         (const unsigned char*)V8t, (const unsigned char*)Vs, (bf16_t*)O, N, Npad, ldo, QB)
-  if (nw == 4) MXL(4, grid, 0); else if (nw == 6) MXL(6, grid, 0); else if (nw == 8) MXL(8, grid, 0);
-  else if (nw == 14) MXL(4, dim3((unsigned)(qb * heads)), qb);      // the product mapping: XCD-contiguous 1-D grid
-  else return -1;
-  DOVE_CHECK_LAUNCH("dove_attention_fwd_mxfp8_nw");
-  return DOVE_OK;
-}
-#endif

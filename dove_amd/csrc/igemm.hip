@@ -20,11 +20,6 @@
 // Epilogue: +bias, GELU(tanh), residual add, row-class-dependent gate (AdaLN-Zero), bf16 store.
 #include "igemm_args.h"
 
-#ifdef DOVE_TIMING_BUILD
-void* g_timing_debug_buf = nullptr;
-extern "C" int dove_timing_set_debug_buf(void* p) { g_timing_debug_buf = p; return 0; }
-#endif
-
 // ------------------------------------------------------------------------------------------------
 // Fast path (up == 0: every conv except the upsample-fused one, and every linear).
 // Same tiling / swizzle / MFMA order as igemm_kernel, but the staging is rebuilt around
@@ -116,16 +111,14 @@ __global__ __launch_bounds__(256) void igemm_fast_kernel(const IgemmArgs a) {
     const auto srd_a = __builtin_amdgcn_make_buffer_rsrc((void*)s_fp, (short)0, (int)frame_bytes, 0x00020000);
     const auto srd_b = __builtin_amdgcn_make_buffer_rsrc((void*)s_wp, (short)0, (int)wtap_bytes, 0x00020000);
     const int soff = s_kc * (BK * 2);
-    if (!(DOVE_DBG(a) & 1)) {
 #pragma unroll
     for (int j = 0; j < NA; ++j) {
       const unsigned voff = (mask[j] & s_tapbit) ? (unsigned)(rowoff[j] + s_tapdelta) : 0x80000000u;
       __builtin_amdgcn_raw_ptr_buffer_load_lds(srd_a, (lds_ptr_t)(smem + BUF * STAGE + (j * 256 + wave * 64) * 16), 16, voff, soff, 0, 0);
     }
-    }
 #pragma unroll
     for (int j = 0; j < NB; ++j) {
-      if (j * 256 + wave * 64 < Cf::B_SLOTS && !(DOVE_DBG(a) & 2))
+      if (j * 256 + wave * 64 < Cf::B_SLOTS)
         __builtin_amdgcn_raw_ptr_buffer_load_lds(srd_b, (lds_ptr_t)(smem + BUF * STAGE + A_BYTES + (j * 256 + wave * 64) * 16), 16,
                                                  (unsigned)boff_g[j], soff, 0, 0);
     }
@@ -183,13 +176,6 @@ __global__ __launch_bounds__(256) void igemm_fast_kernel(const IgemmArgs a) {
       for (int p = 0; p < PT; ++p) xf[p] = *(const bf16x8*)(smem + BUF * STAGE + aoff[p][kk]);
 #pragma unroll
       for (int i = 0; i < CT; ++i) wf[i] = *(const bf16x8*)(smem + BUF * STAGE + A_BYTES + boff[i][kk]);
-      if (DOVE_DBG(a) & 4) {
-#pragma unroll
-        for (int i = 0; i < CT; ++i)
-#pragma unroll
-          for (int p = 0; p < PT; ++p) { asm volatile("" ::"v"(wf[i]), "v"(xf[p])); }
-        continue;
-      }
 #pragma unroll
       for (int i = 0; i < CT; ++i)
 #pragma unroll
@@ -514,14 +500,13 @@ __device__ __forceinline__ void h4_advance(H4State& s, const IgemmArgs& a, const
 // (Round 3 tried two other placements of a step's 2-4 LDS-DMA instructions - spread by sched_group_barrier: -4 %, the compiler also
 // re-clusters the fragment reads; four sched_barrier-fenced quarters of {<= 1 DMA, 4 reads, 8 MFMAs}: +-0.3 % - profiles/r03_halo4x_dma.log.
 // Unlike gemm4x's eight DMAs per step, two to four do not back up the CU's address path; the pinned order below stays.)
-// kM16 (THE PRODUCT since the end of round 4; kM16 = false is the walk of rounds 1-4, kept in the TIMING build for tools/archive/halo_m16_ab.py): the same
-// walk on v_mfma_f32_16x16x32_bf16 - 8 x 8 accumulator blocks of 16 couts x 16 pixels in the same 256 registers, one K-32 fragment per 16 rows
-// (the same 16 ds_read_b128 per step), 64 MFMAs per step split by COUT half: the step's 8 activation fragments and the first 4 weight fragments
+// THE MFMA SHAPE: the walk runs on v_mfma_f32_16x16x32_bf16 - 8 x 8 accumulator blocks of 16 couts x 16 pixels in 256 registers, one K-32 fragment
+// per 16 rows (16 ds_read_b128 per step), 64 MFMAs per step split by COUT half: the step's 8 activation fragments and the first 4 weight fragments
 // are in registers when its barrier opens; the other 4 weight fragments are read under the first 32 MFMAs, the next step's 8 + 4 under the second
 // 32 (two activation register sets, alternating per step).  Why: the chip is power-limited on real operands, and in this shape
 // the matrix pipe alone sustains 2.0-2.1 PF on them against 1.88 PF (half the accumulator traffic per MAC; profiles/r04_mfma_shape_and_order.log).
-// Results are BIT-IDENTICAL to the 32 x 32 x 16 walk (same K order inside the pipe: every form of the kernel and the full-size VAE,
-// profiles/r04_halo_m16.log), 4.3-6.7 % faster at the headline shapes, -14.8 ms per clip.
+// Finding: the 32 x 32 x 16 walk of rounds 1-4 (git history) gave BIT-IDENTICAL results (same K order inside the pipe: every form of the kernel
+// and the full-size VAE, profiles/r04_halo_m16.log) and was 4.3-6.7 % slower at the headline shapes, +14.8 ms per clip.
 // kPart (round 6): the launch's TILE GEOMETRY (H4Geo).  A 16 x 32 tile whose image ends within its first 16 columns (the last tile column when
 // W % 32 is 1..16) spends half of its MFMAs on pixels that do not exist - 6.25 % of a 360-px-wide tile of the tiled VAE.  That column can be
 // walked by a second launch in 32 x 16 tiles (kPart 1): the same 512-pixel register tile, LDS-DMA halo image (34 x 18 halo pixels), weight ring,
@@ -530,19 +515,16 @@ __device__ __forceinline__ void h4_advance(H4State& s, const IgemmArgs& a, const
 // gn_partial slot sums the same pixels in the same order, so outputs AND statistics are bit-identical to the one-launch form.  (First form,
 // commit 93c1943: the last column on HALF a register tile - 32 MFMAs per step against the same weight stream - cost 0.9 of a full tile: a
 // step is then bound by the 64-B requests of the weight tiles.)
-// kFill (TIMING build only, tools/gn_fusion_cost.py): the COST SIDE of a consumer-side GroupNorm + SiLU fusion measured inside the product walk.
-// In steps 2..7 of every group each thread reads the two halo rounds of the next group that have just landed (its own 16-byte slots), runs the
-// instruction mix of normalise + SiLU + pack on their 16 elements (unpack, fma, mul, exp, add, rcp, mul, cvt: 124 VALU, 2 of 8 transcendental,
-// eight independent chains) and writes the ORIGINAL bytes back, so the conv's result is unchanged and the usual tests still hold - what changes
-// is the issue stream: +5 instructions behind most MFMA pairs of six of the nine steps, 2 ds_read_b128 and 2 ds_write_b128 per step.
-template <bool kUp, bool kTiming, bool kPipe = true, bool kSub = false, bool kM16 = false, int kPart = 0, bool kFill = false>
+// Finding (round 6): a consumer-side GroupNorm + SiLU fusion is not worth its issue slots.  Its COST SIDE alone - the instruction mix of normalise +
+// SiLU + pack (124 VALU, 2 ds_read_b128, 2 ds_write_b128 per step) run on the freshly landed halo rounds inside this walk, results unchanged -
+// made the conv 19-20 % slower (profiles/r06_gn_fusion_cost_product_kernel.log; the filler is in git history).
+template <bool kUp, bool kSub = false, int kPart = 0>
 __global__ __launch_bounds__(256, 1) void conv3x3_halo4x_kernel(const IgemmArgs a) {
   using namespace halo8;
   using CFG = typename std::conditional<kSub, Halo4xSubCfg, Halo4xCfg>::type;
   using GEO = H4Geo<kPart>;
   static_assert(!(kUp && kSub), "the sub-pixel form runs on the plain halo geometry of the low-res grid");
-  static_assert(kPart == 0 || (kM16 && !kUp && !kSub && !kTiming && kPipe), "tile geometry 1: the 16 x 16 x 32 walk of the plain conv only");
-  static_assert(!kFill || (kM16 && !kUp && !kSub && !kTiming && kPart == 0), "kFill: the product walk of the plain conv only");
+  static_assert(kPart == 0 || (!kUp && !kSub), "tile geometry 1: the plain conv only");
   // LDS image of the launch's tile geometry (these shadow the halo8 constants of the 16 x 32 tile)
   constexpr int HWID = GEO::HWID, A_BYTES = GEO::A_BYTES, RPW = GEO::RPW;
   constexpr int UHW = halo8::TW / 2 + 2, UHH = halo8::TH / 2 + 2;
@@ -555,8 +537,8 @@ __global__ __launch_bounds__(256, 1) void conv3x3_halo4x_kernel(const IgemmArgs 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   __builtin_assume(wave >= 0 && wave < 4);
-  const int hi = lane >> 5, l31 = lane & 31;
-  const int q4 = lane >> 4, l15 = lane & 15;                  // kM16: fragment row / 16-byte K chunk of the 16 x 16 x 32 shape
+  const int hi = lane >> 5, l31 = lane & 31;                  // lane roles of the retired 32 x 32 x 16 walk: see PINNED below
+  const int q4 = lane >> 4, l15 = lane & 15;                  // fragment row / 16-byte K chunk of the 16 x 16 x 32 shape
 
   // PERSISTENT workgroups: block b walks tiles b, b + G, b + 2G, ... as ONE continuous K walk of (frame tap, channel
   // chunk) GROUPS of 9 spatial taps.  While group `cur` is multiplied, the halo of group `nxt` (the next group of this
@@ -574,7 +556,6 @@ __global__ __launch_bounds__(256, 1) void conv3x3_halo4x_kernel(const IgemmArgs 
   kc.wtap_stride = (long long)a.Cout_pad * a.Cin;
   kc.tid = tid;
   const int ntiles = kc.ntiles, G = kc.G;
-  const int ngroups = a.kt * kc.kcn;
   const long long wtap_stride = kc.wtap_stride;
 
   unsigned voffB[2];
@@ -613,13 +594,16 @@ __global__ __launch_bounds__(256, 1) void conv3x3_halo4x_kernel(const IgemmArgs 
                                                0, 0, 0);
     b_wp += wtap_stride;
   };
-  auto stage_b_half = [&](auto slotc, auto jc, int nrec) {     // kM16: one of stage_b's two instructions (the caller moves the stream pointer)
+  auto stage_b_half = [&](auto slotc, auto jc, int nrec) {     // one of stage_b's two instructions, issued from inside the MFMA stream (the caller moves the stream pointer)
     constexpr int slot = decltype(slotc)::value, j = decltype(jc)::value;
     const auto srd = __builtin_amdgcn_make_buffer_rsrc((void*)b_wp, (short)0, nrec, 0x00020000);
     __builtin_amdgcn_raw_ptr_buffer_load_lds(srd, (lds_ptr_t)(smem + B0 + slot * B_BYTES + j * 4096 + wave * 1024), 16, voffB[j], 0, 0, 0);
   };
 
-  // weight fragment offsets: 4 cout tiles x 2 k-halves (slot 0), XOR-swizzled 64-B rows
+  // PINNED: two leftovers of the 32 x 32 x 16 walk of rounds 1-4 (git history) that compute nothing the kernel uses, but whose removal changes
+  // the code hipcc emits for the rest (tools/isa_equal.py against 728c3f6): without this table the <kUp> kernel's prologue is scheduled
+  // differently; without `hi` and `l31` among the captures of the epilogue's `wr` all four kernels get another register allocation.  They go
+  // with the next change that is allowed to move instructions and is measured on the GPU.
   int boff[4][2];
 #pragma unroll
   for (int kk = 0; kk < 2; ++kk)
@@ -629,12 +613,12 @@ __global__ __launch_bounds__(256, 1) void conv3x3_halo4x_kernel(const IgemmArgs 
       boff[i][kk] = B0 + row * ROWB + (((kk * 2 + hi) ^ ((row >> 2) & 3)) << 4);
     }
   // activation fragment bases (padded 80-B halo rows -> base + immediate for every tap and either buffer)
-  const int abase0 = kM16 ? ((RPW * wave) * HWID + l15) * APITCH + q4 * 16 : ((4 * wave) * HWID + l31) * APITCH + hi * 16;
+  const int abase0 = ((RPW * wave) * HWID + l15) * APITCH + q4 * 16;
   int abaseU[3];
 #pragma unroll
   for (int dw = 0; dw < 3; ++dw)
-    abaseU[dw] = kM16 ? ((2 * wave) * UHW + 1 + ((l15 + dw - 1) >> 1)) * APITCH + q4 * 16 : ((2 * wave) * UHW + 1 + ((l31 + dw - 1) >> 1)) * APITCH + hi * 16;
-  // kM16: weight rows 16 i + l15 share (row >> 2) & 3 = (l15 >> 2) & 3, so the staging-side XOR swizzle leaves ONE base + i * 16 rows
+    abaseU[dw] = ((2 * wave) * UHW + 1 + ((l15 + dw - 1) >> 1)) * APITCH + q4 * 16;
+  // weight rows 16 i + l15 share (row >> 2) & 3 = (l15 >> 2) & 3, so the staging-side XOR swizzle leaves ONE base + i * 16 rows
   const int bbase16 = B0 + l15 * ROWB + ((q4 ^ ((l15 >> 2) & 3)) << 4);
 
   // ---- prologue (once per workgroup): whole first halo + the first BAHEAD weight taps ----
@@ -664,7 +648,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_halo4x_kernel(const IgemmArgs 
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
 
-  // fragment loaders: every address is a base VGPR + an immediate
+  // fragment addresses: every one is a base VGPR + an immediate
   // (kSub: the four taps of a group sit at halo offset (py + a, px + b) - per-tile bases abaseT[tap]; abaseN0 = tap 0 of the NEXT group's tile)
   int abaseT[4] = {0, 0, 0, 0}, abaseN0 = 0;
   auto sub_bases = [&](int ph, int (&bt)[4]) {
@@ -672,41 +656,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_halo4x_kernel(const IgemmArgs 
 #pragma unroll
     for (int tp = 0; tp < 4; ++tp) bt[tp] = abase0 + ((py + (tp >> 1)) * HWID + px + (tp & 1)) * APITCH;
   };
-  auto load_a = [&](auto tapc, auto kkc, auto bufc, bf16x8 (&xf)[4]) {
-    constexpr int tap = decltype(tapc)::value, kk = decltype(kkc)::value, gb = decltype(bufc)::value * A_BYTES;
-    constexpr int dh = tap / 3, dw = tap % 3;
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      if (kSub) {
-        xf[p] = *(const bf16x8*)(smem + abaseT[tap & 3] + gb + p * HWID * APITCH + kk * 32);
-      } else if (kUp) {
-        const int rowimm = ((p + dh + 1) >> 1) * UHW * APITCH;
-        xf[p] = *(const bf16x8*)(smem + abaseU[dw] + gb + rowimm + kk * 32);
-      } else {
-        xf[p] = *(const bf16x8*)(smem + abase0 + gb + ((p + dh) * HWID + dw) * APITCH + kk * 32);
-      }
-    }
-  };
-  auto load_a_next0 = [&](auto bufc, bf16x8 (&xf)[4]) {           // kSub: k-half 0 of tap 0 of group nxt (possibly another tile, another phase)
-    constexpr int gb = decltype(bufc)::value * A_BYTES;
-#pragma unroll
-    for (int p = 0; p < 4; ++p) xf[p] = *(const bf16x8*)(smem + abaseN0 + gb + p * HWID * APITCH);
-  };
-  auto load_b = [&](auto kkc, auto slotc, bf16x8 (&wf)[4]) {
-    constexpr int kk = decltype(kkc)::value, slot = decltype(slotc)::value;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) wf[i] = *(const bf16x8*)(smem + boff[i][kk] + slot * B_BYTES);
-  };
-  f32x16 acc[4][4];
-  auto mma = [&](const bf16x8 (&wf)[4], const bf16x8 (&xf)[4]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int p = 0; p < 4; ++p)
-        acc[i][p] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[i], xf[p], acc[i][p], 0, 0, 0);
-  };
-
-  // ---- kM16: the 16 x 16 x 32 walk.  Fragment idx = 2 p + j of a step: tile row p, columns 16 j .. 16 j + 15 (one K-32 fragment each) ----
+  // Fragment idx = 2 p + j of a step: tile row p, columns 16 j .. 16 j + 15 (one K-32 fragment each)
   auto a16_addr = [&](auto tapc, auto bufc, int idx) -> int {
     constexpr int tap = decltype(tapc)::value, gb = decltype(bufc)::value * A_BYTES;
     constexpr int dh = tap / 3, dw = tap % 3;
@@ -733,53 +683,10 @@ __global__ __launch_bounds__(256, 1) void conv3x3_halo4x_kernel(const IgemmArgs 
     asm("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc16[k]) : "v"(w), "v"(x));
   };
 
-  // ---- kFill: see the kernel's header ----
-  u32x4 fd[2];                                     // the two rounds' 16 bytes per lane (8 bf16 each)
-  float ff[8], ft[8];
-  unsigned fp4[4];
-  float f_scale = 1.0f, f_shift = 0.0f;
-  if (kFill) {                                     // opaque per-lane values (a real fusion holds the lane's channel scale / shift here)
-    f_scale = 1.0f + (float)lane * 0.0009765625f; f_shift = (float)(lane & 7) * 0.03125f;
-    asm volatile("" : "+v"(f_scale), "+v"(f_shift));
-  }
-  auto fill_op = [&](int q, int rnd) {             // op q (0..63) of round rnd: stage q >> 3 of element q & 7 (eight independent chains)
-    const int e = q & 7, stg = q >> 3;
-    const unsigned dw = rnd ? fd[1][e >> 1] : fd[0][e >> 1];
-    switch (stg) {
-      case 0: if (e & 1) asm volatile("v_and_b32 %0, 0xffff0000, %1" : "=v"(ff[e]) : "v"(dw)); else asm volatile("v_lshlrev_b32 %0, 16, %1" : "=v"(ff[e]) : "v"(dw)); break;
-      case 1: asm volatile("v_fma_f32 %0, %0, %1, %2" : "+v"(ff[e]) : "v"(f_scale), "v"(f_shift)); break;   // per-channel scale / shift live in registers
-      case 2: asm volatile("v_mul_f32 %0, %1, %2" : "=v"(ft[e]) : "s"(-1.4426950408889634f), "v"(ff[e])); break;
-      case 3: asm volatile("v_exp_f32 %0, %0" : "+v"(ft[e])); break;
-      case 4: asm volatile("v_add_f32 %0, 1.0, %0" : "+v"(ft[e])); break;
-      case 5: asm volatile("v_rcp_f32 %0, %0" : "+v"(ft[e])); break;
-      case 6: asm volatile("v_mul_f32 %0, %0, %1" : "+v"(ff[e]) : "v"(ft[e])); break;
-      default: if (!(e & 1)) asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(fp4[e >> 1]) : "v"(ff[e]), "v"(ff[e + 1])); break;
-    }
-  };
-  auto fill_slot = [&](int slot, int tap_, int nbuf) {   // slot 0..31 of step tap_; nbuf = the halo buffer of group nxt
-    if (!kFill || tap_ < 2 || tap_ > 7) return;
-    char* const base = smem + nbuf * A_BYTES + (2 * (tap_ - 2)) * 4096 + wave * 1024 + lane * 16;
-    if (slot == 0) fd[0] = *(const u32x4*)base;
-    if (slot == 1) fd[1] = *(const u32x4*)(base + 4096);
-    if (slot >= 6 && slot < 32) {                  // 26 slots x 5 ops >= 2 rounds x 64 ops (the last two slots also carry the write-back)
-      for (int j = 0; j < 5; ++j) {
-        const int q = (slot - 6) * 5 + j;
-        if (q < 128) fill_op(q & 63, q >> 6);
-      }
-    }
-    if (slot == 30) { asm volatile("" :: "v"(fp4[0]), "v"(fp4[1]), "v"(fp4[2]), "v"(fp4[3])); *(u32x4*)base = fd[0]; }
-    if (slot == 31) { asm volatile("" :: "v"(fp4[0]), "v"(fp4[1]), "v"(fp4[2]), "v"(fp4[3])); *(u32x4*)(base + 4096) = fd[1]; }
-  };
-
-  bf16x8 xa[4], wa[4], xb[4], wb[4];              // fragment sets: a = k-half 0, b = k-half 1
-  bf16x8 xs[2][8], wl[4], wh[4];                  // kM16: activation sets (alternating per step), cout-low / cout-high weight fragments
+  bf16x8 xs[2][8], wl[4], wh[4];                  // activation sets (alternating per step), cout-low / cout-high weight fragments
   if (kSub) sub_bases(h4_decode(a, kc, (int)blockIdx.x).ph, abaseT);
-  if (!kM16) {                                    // (kM16 reads its first fragments at the top of every tile: see the tile loop)
-    load_a(I0{}, I0{}, I0{}, xa);
-    load_b(I0{}, I0{}, wa);
-  }
 
-  // one K-step = one spatial tap of group cur (parity par); fragments of k-half 0 are already in xa/wa
+  // one K-step = one spatial tap of group cur (parity par); its 8 activation and 4 cout-low weight fragments are already in xs / wl
   auto step = [&](auto tapc, auto parc) {
     constexpr int tap = decltype(tapc)::value, par = decltype(parc)::value;
     constexpr int NH = CFG::nh(tap, NR);                       // halo rounds staged in this step
@@ -792,91 +699,50 @@ __global__ __launch_bounds__(256, 1) void conv3x3_halo4x_kernel(const IgemmArgs 
     __builtin_amdgcn_s_barrier();                                  // then the step barrier (LDS hand-off point)
     __builtin_amdgcn_sched_barrier(0);
     // ---- from here to the end of the step: ONE basic block ----
-    if (!kM16) {
-      if (stap == NT) b_wp = wg_nxt;
-      stage_b(std::integral_constant<int, (stap + NT * par) % BR>{}, stap < NT ? nrec_b_cur : nrec_b_nxt);
-      if (NH >= 1) stage_halo_round(std::integral_constant<int, (NH >= 1 ? R0 : 0)>{}, NPar{});
-      if (NH >= 2) stage_halo_round(std::integral_constant<int, (NH >= 2 ? R0 + 1 : 0)>{}, NPar{});
-      if (NH >= 3) stage_halo_round(std::integral_constant<int, (NH >= 3 ? R0 + 2 : 0)>{}, NPar{});
-      if (NH >= 4) stage_halo_round(std::integral_constant<int, (NH >= 4 ? R0 + 3 : 0)>{}, NPar{});
-      if (NH >= 5) stage_halo_round(std::integral_constant<int, (NH >= 5 ? R0 + 4 : 0)>{}, NPar{});
-      if (NH >= 6) stage_halo_round(std::integral_constant<int, (NH >= 6 ? R0 + 5 : 0)>{}, NPar{});
-    }
-    if (kM16) {
-      // (the staging calls above are NOT made for kM16 - see the guard - they are issued from inside the MFMA stream below)
-      constexpr int SP = (tap + NT * par) & 1;                     // this step's activation register set (steps alternate; trips are even)
-      using SlotCur = std::integral_constant<int, (tap + NT * par) % BR>;
-      using SlotNxt = std::integral_constant<int, (tap + 1 + NT * par) % BR>;
-      // first half: cout blocks 0-3 (wl) x the 8 pixel blocks.  Behind every pair of MFMAs ONE other instruction, in a fixed order
-      // (sched_barrier-fenced: the MFMA mask of sched_group_barrier does not see an asm MFMA): the 4 cout-high fragments this step's
-      // second half needs, then the step's LDS-DMAs (2 weight halves + NH halo rounds)
+    constexpr int SP = (tap + NT * par) & 1;                   // this step's activation register set (steps alternate; trips are even)
+    using SlotCur = std::integral_constant<int, (tap + NT * par) % BR>;
+    using SlotNxt = std::integral_constant<int, (tap + 1 + NT * par) % BR>;
+    // first half: cout blocks 0-3 (wl) x the 8 pixel blocks.  Behind every pair of MFMAs ONE other instruction, in a fixed order
+    // (sched_barrier-fenced: the MFMA mask of sched_group_barrier does not see an asm MFMA): the 4 cout-high fragments this step's
+    // second half needs, then the step's LDS-DMAs (2 weight halves + NH halo rounds)
 #pragma unroll
-      for (int g = 0; g < 16; ++g) {
-        mfma16(2 * g, wl[(2 * g) >> 3], xs[SP][(2 * g) & 7]);
-        mfma16(2 * g + 1, wl[(2 * g + 1) >> 3], xs[SP][(2 * g + 1) & 7]);
-        if (g < 4) wh[g] = *(const bf16x8*)(smem + b16_addr(SlotCur{}, 4 + g));
-        if (g == 4) {
-          if (stap == NT) b_wp = wg_nxt;
-          stage_b_half(std::integral_constant<int, (stap + NT * par) % BR>{}, I0{}, stap < NT ? nrec_b_cur : nrec_b_nxt);
-        }
-        if (g == 5) {
-          stage_b_half(std::integral_constant<int, (stap + NT * par) % BR>{}, I1{}, stap < NT ? nrec_b_cur : nrec_b_nxt);
-          b_wp += wtap_stride;
-        }
-        if (g == 6 && NH >= 1) stage_halo_round(std::integral_constant<int, (NH >= 1 ? R0 : 0)>{}, NPar{});
-        if (g == 7 && NH >= 2) stage_halo_round(std::integral_constant<int, (NH >= 2 ? R0 + 1 : 0)>{}, NPar{});
-        if (g == 8 && NH >= 3) stage_halo_round(std::integral_constant<int, (NH >= 3 ? R0 + 2 : 0)>{}, NPar{});
-        if (g == 9 && NH >= 4) stage_halo_round(std::integral_constant<int, (NH >= 4 ? R0 + 3 : 0)>{}, NPar{});
-        if (g == 10 && NH >= 5) stage_halo_round(std::integral_constant<int, (NH >= 5 ? R0 + 4 : 0)>{}, NPar{});
-        if (g == 11 && NH >= 6) stage_halo_round(std::integral_constant<int, (NH >= 6 ? R0 + 5 : 0)>{}, NPar{});
-        fill_slot(g, tap, 1 - par);
-        __builtin_amdgcn_sched_barrier(0);
+    for (int g = 0; g < 16; ++g) {
+      mfma16(2 * g, wl[(2 * g) >> 3], xs[SP][(2 * g) & 7]);
+      mfma16(2 * g + 1, wl[(2 * g + 1) >> 3], xs[SP][(2 * g + 1) & 7]);
+      if (g < 4) wh[g] = *(const bf16x8*)(smem + b16_addr(SlotCur{}, 4 + g));
+      if (g == 4) {
+        if (stap == NT) b_wp = wg_nxt;
+        stage_b_half(std::integral_constant<int, (stap + NT * par) % BR>{}, I0{}, stap < NT ? nrec_b_cur : nrec_b_nxt);
       }
-      // second half: cout blocks 4-7 (wh); behind the first 12 pairs the next step's 8 activation + 4 cout-low weight fragments
-      // (last tap: tap 0 of group nxt - after a tile's last group that is the NEXT tile's first, which the tile loop reads again)
-#pragma unroll
-      for (int g = 0; g < 16; ++g) {
-        mfma16(32 + 2 * g, wh[(2 * g) >> 3], xs[SP][(2 * g) & 7]);
-        mfma16(32 + 2 * g + 1, wh[(2 * g + 1) >> 3], xs[SP][(2 * g + 1) & 7]);
-        if (g < 8) {
-          int ad;
-          if (tap < NT - 1) ad = a16_addr(std::integral_constant<int, (tap + 1) % NT>{}, Par{}, g);
-          else if (kSub) ad = a16_addr_next0(NPar{}, g);
-          else ad = a16_addr(I0{}, NPar{}, g);
-          xs[SP ^ 1][g] = *(const bf16x8*)(smem + ad);
-        } else if (g < 12) {
-          wl[g - 8] = *(const bf16x8*)(smem + b16_addr(SlotNxt{}, g - 8));
-        }
-        fill_slot(16 + g, tap, 1 - par);
-        __builtin_amdgcn_sched_barrier(0);
+      if (g == 5) {
+        stage_b_half(std::integral_constant<int, (stap + NT * par) % BR>{}, I1{}, stap < NT ? nrec_b_cur : nrec_b_nxt);
+        b_wp += wtap_stride;
       }
-      return;
+      if (g == 6 && NH >= 1) stage_halo_round(std::integral_constant<int, (NH >= 1 ? R0 : 0)>{}, NPar{});
+      if (g == 7 && NH >= 2) stage_halo_round(std::integral_constant<int, (NH >= 2 ? R0 + 1 : 0)>{}, NPar{});
+      if (g == 8 && NH >= 3) stage_halo_round(std::integral_constant<int, (NH >= 3 ? R0 + 2 : 0)>{}, NPar{});
+      if (g == 9 && NH >= 4) stage_halo_round(std::integral_constant<int, (NH >= 4 ? R0 + 3 : 0)>{}, NPar{});
+      if (g == 10 && NH >= 5) stage_halo_round(std::integral_constant<int, (NH >= 5 ? R0 + 4 : 0)>{}, NPar{});
+      if (g == 11 && NH >= 6) stage_halo_round(std::integral_constant<int, (NH >= 6 ? R0 + 5 : 0)>{}, NPar{});
+      __builtin_amdgcn_sched_barrier(0);
     }
-    load_a(tapc, I1{}, Par{}, xb);
-    load_b(I1{}, std::integral_constant<int, (tap + NT * par) % BR>{}, wb);
-    mma(wa, xa);
-    // next step's k-half 0 (last tap: tap 0 of group nxt - after a tile's last group that is the NEXT tile's first)
-    if (tap < NT - 1) load_a(std::integral_constant<int, (tap + 1) % NT>{}, I0{}, Par{}, xa);
-    else if (kSub) load_a_next0(NPar{}, xa);
-    else load_a(I0{}, I0{}, NPar{}, xa);
-    load_b(I0{}, std::integral_constant<int, (tap + 1 + NT * par) % BR>{}, wa);
-    mma(wb, xb);
-    // pinned interleave: the staging work and one fragment read per MFMA gap
+    // second half: cout blocks 4-7 (wh); behind the first 12 pairs the next step's 8 activation + 4 cout-low weight fragments
+    // (last tap: tap 0 of group nxt - after a tile's last group that is the NEXT tile's first, which the tile loop reads again)
 #pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                // 1 MFMA
-      if (i < 2 + NH) {
-        __builtin_amdgcn_sched_group_barrier(0x004, 4, 0);              // <= 4 SALU (descriptor, m0)
-        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);              // 1 VMEM read (LDS-DMA)
+    for (int g = 0; g < 16; ++g) {
+      mfma16(32 + 2 * g, wh[(2 * g) >> 3], xs[SP][(2 * g) & 7]);
+      mfma16(32 + 2 * g + 1, wh[(2 * g + 1) >> 3], xs[SP][(2 * g + 1) & 7]);
+      if (g < 8) {
+        int ad;
+        if (tap < NT - 1) ad = a16_addr(std::integral_constant<int, (tap + 1) % NT>{}, Par{}, g);
+        else if (kSub) ad = a16_addr_next0(NPar{}, g);
+        else ad = a16_addr(I0{}, NPar{}, g);
+        xs[SP ^ 1][g] = *(const bf16x8*)(smem + ad);
+      } else if (g < 12) {
+        wl[g - 8] = *(const bf16x8*)(smem + b16_addr(SlotNxt{}, g - 8));
       }
-      if (i >= CFG::DS0 && i < CFG::DS0 + 8) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);   // 1 ds_read (k-half 1)
+      __builtin_amdgcn_sched_barrier(0);
     }
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-      if (i < 8) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);     // next step's k-half 0 fragments
-    }
-    __builtin_amdgcn_sched_barrier(0);
   };
   auto group = [&](auto parc) {
     step(std::integral_constant<int, 0>{}, parc); step(std::integral_constant<int, 1>{}, parc);
@@ -890,10 +756,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_halo4x_kernel(const IgemmArgs 
 
   // epilogue-side lane role: 8 lanes x 8 channels cover 64 channels (128 B) of one pixel
   const int e_px = lane >> 3, e_ch = lane & 7;
-  unsigned long long tm_walk = 0, tm_bar = 0, tm_body = 0, tm_drain = 0, tm_n = 0, tm0 = 0, tm1 = 0, tm2 = 0, tm3 = 0;
-  const unsigned long long tm_start = kTiming ? __builtin_amdgcn_s_memtime() : 0;
   for (int tile = (int)blockIdx.x; tile < ntiles; tile += G) {
-    if (kTiming) tm0 = __builtin_amdgcn_s_memtime();
     const H4Tile c = h4_decode<kPart>(a, kc, tile);
     f32x4 bias_r[2][2];                                       // this lane's 8 channels in each 64-channel half
 #pragma unroll
@@ -902,17 +765,8 @@ __global__ __launch_bounds__(256, 1) void conv3x3_halo4x_kernel(const IgemmArgs 
       bias_r[h][0] = bias_r[h][1] = f32x4{0.f, 0.f, 0.f, 0.f};
       if (a.bias) { bias_r[h][0] = *(const f32x4*)(a.bias + cbh); bias_r[h][1] = *(const f32x4*)(a.bias + cbh + 4); }
     }
-    if (kM16) {
 #pragma unroll
-      for (int k = 0; k < 64; ++k) acc16[k] = f32x4{0.f, 0.f, 0.f, 0.f};
-    } else {
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int p = 0; p < 4; ++p)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[i][p][r] = 0.f;
-    }
+    for (int k = 0; k < 64; ++k) acc16[k] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     // a tile has an even number of groups (Cin % 64 == 0): two per trip, one of each halo-buffer parity - straight-line,
     // so there is no control-flow merge at which the register allocator would have to reconcile two step bodies
@@ -924,14 +778,12 @@ __global__ __launch_bounds__(256, 1) void conv3x3_halo4x_kernel(const IgemmArgs 
       sub_bases(h4_decode(a, kc, tile + G).ph, nb4);
       next_base0 = nb4[0];
     }
-    if (kM16) {
-      // The tile's first fragments are read HERE, not carried over from the previous tile's last step like the 32 x 32 x 16 walk does: 12
-      // fragments alive across the epilogue are 48 registers the epilogue does not have (one exposed LDS latency per tile of >= 72 steps)
+    // The tile's first fragments are read HERE, not carried over from the previous tile's last step (which prefetched them): 12 fragments
+    // alive across the epilogue are 48 registers the epilogue does not have (one exposed LDS latency per tile of >= 72 steps)
 #pragma unroll
-      for (int idx = 0; idx < 8; ++idx) xs[0][idx] = *(const bf16x8*)(smem + a16_addr(I0{}, I0{}, idx));
+    for (int idx = 0; idx < 8; ++idx) xs[0][idx] = *(const bf16x8*)(smem + a16_addr(I0{}, I0{}, idx));
 #pragma unroll
-      for (int ib = 0; ib < 4; ++ib) wl[ib] = *(const bf16x8*)(smem + b16_addr(I0{}, ib));
-    }
+    for (int ib = 0; ib < 4; ++ib) wl[ib] = *(const bf16x8*)(smem + b16_addr(I0{}, ib));
     for (int g = 0; g < ng_tile; g += 2) {
       if (kSub) abaseN0 = abaseT[0];                            // group(I0)'s last step prefetches this tile's next group
       group(I0{});
@@ -952,9 +804,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_halo4x_kernel(const IgemmArgs 
     // wave transposes through its own 12 KB slice of the halo buffer the last group just finished with (the other one
     // already holds the next tile's first halo), one tile row x 64 channels at a time in fp32 (bias and residual are
     // added before the single bf16 rounding), and stores 16 B per lane with 8 lanes covering a full 128-B line. ----
-    if (kTiming) tm1 = __builtin_amdgcn_s_memtime();
     __builtin_amdgcn_s_barrier();                            // every wave is done reading that buffer
-    if (kTiming) tm2 = __builtin_amdgcn_s_memtime();
     {
       constexpr int EROW = 272;                              // 64 fp32 per pixel + 16 pad
       char* const eslice = smem + A_BYTES + wave * 12288;      // (a tile's last group has parity 1)
@@ -991,23 +841,13 @@ __global__ __launch_bounds__(256, 1) void conv3x3_halo4x_kernel(const IgemmArgs 
         for (int h = 0; h < 2; ++h)
 #pragma unroll
           for (int q2 = 0; q2 < 2; ++q2) { gs[h][q2] = f32x2{0.f, 0.f}; gq[h][q2] = f32x2{0.f, 0.f}; }
-        auto wr = [&](int p, int h) {                          // accumulators of tile row p, channel half h -> the wave's slice (fp32)
-          if (kM16) {                                            // four 16-cout blocks x two 16-pixel blocks, one register quad each
+        // accumulators of tile row p, channel half h -> the wave's slice (fp32): four 16-cout blocks x two 16-pixel blocks, one register quad each
+        auto wr = [&](int p, int h) {
 #pragma unroll
-            for (int ib = 0; ib < 4; ++ib)
+          for (int ib = 0; ib < 4; ++ib)
 #pragma unroll
-              for (int j = 0; j < 2; ++j) *(f32x4*)(eslice + (16 * j + l15) * EROW + (ib * 16 + 4 * q4) * 4) = acc16[(h * 4 + ib) * 8 + 2 * p + j];
-            return;
-          }
-#pragma unroll
-          for (int i2 = 0; i2 < 2; ++i2)
-#pragma unroll
-            for (int gq = 0; gq < 4; ++gq) {
-              f32x4 o;
-#pragma unroll
-              for (int e = 0; e < 4; ++e) o[e] = acc[h * 2 + i2][p][gq * 4 + e];
-              *(f32x4*)(eslice + l31 * EROW + (i2 * 32 + 8 * gq + 4 * hi) * 4) = o;
-            }
+            for (int j = 0; j < 2; ++j) *(f32x4*)(eslice + (16 * j + l15) * EROW + (ib * 16 + 4 * q4) * 4) = acc16[(h * 4 + ib) * 8 + 2 * p + j];
+          (void)hi; (void)l31;                                 // PINNED captures: see the kernel's prologue
         };
         // GroupNorm partial sums -> gn_partial.  A row of gn_partial belongs to (16 x 32 tile, wave slot 0..3) of the conv's tile grid whatever
         // the launch's geometry, and holds the sums over THAT slot's pixels (tile rows 4 s .. 4 s + 3) in the 16 x 32 form's order.  A wave of
@@ -1048,7 +888,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_halo4x_kernel(const IgemmArgs 
             }
           }
         };
-        if (kPipe) wr(0, 0);
+        wr(0, 0);
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
           const int oh = c.oh0 + RPW * wave + (kPart == 1 ? 2 * p : p);
@@ -1076,7 +916,6 @@ __global__ __launch_bounds__(256, 1) void conv3x3_halo4x_kernel(const IgemmArgs 
 #pragma unroll
               for (int it = 0; it < 4; ++it) rr[it] = __builtin_amdgcn_raw_buffer_load_b128(srd_r, (int)ro[it], h * 128, 0);
             }
-            if (!kPipe) wr(p, h);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // wave-private slice: no barrier needed
             f32x4 lo[4], hi4[4];
 #pragma unroll
@@ -1087,7 +926,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_halo4x_kernel(const IgemmArgs 
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             // the next block's accumulators go into the slice NOW: its reads above are complete, and the write latency then runs under
             // this block's bias / residual / statistics arithmetic and stores instead of in front of the next block's reads
-            if (kPipe && (p < 3 || h < 1)) wr(h ? p + 1 : p, h ^ 1);
+            if (p < 3 || h < 1) wr(h ? p + 1 : p, h ^ 1);
 #pragma unroll
             for (int it = 0; it < 4; ++it) {
               f32x4 x0 = lo[it] + bias_r[h][0], x1 = hi4[it] + bias_r[h][1];
@@ -1131,41 +970,26 @@ __global__ __launch_bounds__(256, 1) void conv3x3_halo4x_kernel(const IgemmArgs 
     }
     // the counted-vmcnt scheme of the K walk restarts from an empty queue (stores count in vmcnt on gfx9; the loads of
     // the next tile's first steps were issued before them and have long landed)
-    if (kTiming) tm3 = __builtin_amdgcn_s_memtime();
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (kTiming) {
-      const unsigned long long tm4 = __builtin_amdgcn_s_memtime();
-      tm_walk += tm1 - tm0; tm_bar += tm2 - tm1; tm_body += tm3 - tm2; tm_drain += tm4 - tm3; ++tm_n;
-    }
-  }
-  if (kTiming && a.gate && blockIdx.x == 100 && lane == 0) {       // TIMING build: `gate` is the host's debug buffer
-    unsigned long long* o = (unsigned long long*)a.gate + wave * 8;
-    o[0] = tm_walk; o[1] = tm_bar; o[2] = tm_body; o[3] = tm_drain; o[4] = tm_n; o[5] = (unsigned long long)ngroups * 9;
-    o[6] = __builtin_amdgcn_s_memtime() - tm_start;
   }
 }
 
 // ------------------------------------------------------------------------------------------------
 // Plain GEMM  out[M][N] = x[M][K] * w[N][K]^T  (DiT linears, 1x1x1 convs over a contiguous channels-last tensor): 256 x 256 workgroup
-// tiles walked by PERSISTENT workgroups in an XCD-aware supertile order (g4_* below), operands staged by LDS-DMA, the LDS-transposed epilogue
-// with buffer-addressed stores (bias, GELU(tanh), residual and AdaLN gate applied in fp32 on the read side).
-//   gemm8p_kernel (the product): eight waves in ping-pong over two K-64 buffers of full 128-B rows - see its header.
-//   gemm4x_kernel (round 2's kernel, TIMING build only, for the within-run A/B of tools/archive/gemm8p_ab.py): ONE wave per SIMD (512-register
-//     budget), 4 waves = 2 x 2 wave tiles of 128 x 128, 4-stage K-32 ring staged 3 steps ahead with counted vmcnt, fragments
-//     register-pipelined across the single per-step barrier, pinned MFMA / VMEM / DS interleave.
-// (gemm4x's tile constants, the supertile walk g4_* and IgemmArgs live in igemm_args.h; gemm4x_kernel itself in gemm4x_timing.hip)
-
-// ------------------------------------------------------------------------------------------------
-// gemm8p: gemm4x's GEMM (same 256 x 256 tile, same persistent tile walk and supertile order, same arithmetic: results are bit-identical)
+// tiles walked by PERSISTENT workgroups in an XCD-aware supertile order (g4_* in igemm_args.h), operands staged by LDS-DMA, the LDS-transposed
+// epilogue with buffer-addressed stores (bias, GELU(tanh), residual and AdaLN gate applied in fp32 on the read side).
+//
+// gemm8p_kernel succeeds round 2's gemm4x_kernel (git history: ONE wave per SIMD, 4 waves = 2 x 2 wave tiles of 128 x 128, a 4-stage K-32 ring
+// staged 3 steps ahead): same 256 x 256 tile, same persistent tile walk and supertile order, same arithmetic - results are bit-identical -
 // with the two changes the measurements of round 3 asked for.
-//  * FULL-LINE STAGING.  gemm4x's K-32 ring is filled by LDS-DMA instructions that fetch 16 rows x 64 B; a DMA-only kernel walking the same
+//  * FULL-LINE STAGING.  gemm4x's K-32 ring was filled by LDS-DMA instructions that fetch 16 rows x 64 B; a DMA-only kernel walking the same
 //    tiles (tools/archive/stage_ab.py) stages at 11-14.5 TB/s that way - as long as the MFMA work itself takes - and 1.5-1.65x faster with 8 rows
 //    x 128 B per instruction (64-B requests run into the L2 request rate: 11 requests per clock and XCD of 16; TA busy 78 %), while the
 //    queue depth hardly matters (nothing in flight behind a 64 KB step: -9 %).  So the ring here is TWO K-64 buffers of 128-B rows
 //    (XOR-swizzled like attention's K tile), each refilled in one go as soon as its last reader is through.
 //  * PING-PONG.  Eight waves = two per SIMD; a wave owns 128 tokens x 64 channels (128 accumulator registers of its 256) and alternates
 //        LOAD(q):  12 fragment reads of K-32 phase q (48 registers) [+ on even q its 8 LDS-DMAs: the K-64 step after this one]
-//        MFMA(q):  16 MFMAs, nothing else in the stream
+//        MFMA(q):  32 MFMAs, nothing else in the stream
 //    between workgroup barriers, the waves 4-7 (token rows 128-255) ONE barrier behind the waves 0-3: on every SIMD one wave computes
 //    while its partner loads, and the pipe is handed over at each barrier with the last MFMA of one wave still executing.
 //        slot 2q:   waves 0-3 LOAD(q)      waves 4-7 MFMA(q-1)
@@ -1181,12 +1005,12 @@ constexpr int XB = 0, WB = 2 * OPB;                          // x buffers at 0 /
 constexpr int EPI = 4 * OPB;                                 // epilogue staging: 8 waves x 32 rows x 128 B (XOR-swizzled)
 constexpr int LDS_BYTES = EPI + 8 * 4096;                    // 163840
 }  // namespace gemm8p
-// kM16 (THE PRODUCT since the end of round 4; kM16 = false = round 3's phases, kept in the TIMING build for tools/archive/gemm_m16_ab.py, DOVE_GEMM_M16=0):
-// the same phases on v_mfma_f32_16x16x32_bf16 - the MFMA shape the power-limited pipe sustains best on real operands and to which the dominant
-// conv moved.  A wave's 128 tokens x 64 channels = 8 x 4 blocks of 16 x 16 (the same 128 accumulator registers), a phase =
-// 12 K-32 fragment reads + 32 MFMAs.  Results are BIT-IDENTICAL to the 32 x 32 x 16 phases on every form the DiT uses (so the row tails on
-// igemm_fast still sum like the main launch), 3-7 % faster at N = 18 226: qkv 1.29 -> 1.38 PF, ff1 1.26 -> 1.34 PF (profiles/r04_gemm_m16.log).
-template <bool kAct, bool kGate, bool kTiming = false, bool kM16 = false>
+// The phases run on v_mfma_f32_16x16x32_bf16 - the MFMA shape the power-limited pipe sustains best on real operands and to which the dominant
+// conv moved.  A wave's 128 tokens x 64 channels = 8 x 4 blocks of 16 x 16 (128 accumulator registers), a phase =
+// 12 K-32 fragment reads + 32 MFMAs.  Finding: round 3's 32 x 32 x 16 phases (git history) gave BIT-IDENTICAL results on every form the DiT uses
+// (so the row tails on igemm_fast still sum like the main launch) and were 3-7 % slower at N = 18 226: qkv 1.29 -> 1.38 PF, ff1 1.26 -> 1.34 PF
+// (profiles/r04_gemm_m16.log).
+template <bool kAct, bool kGate>
 __global__ __launch_bounds__(512, 2) void gemm8p_kernel(const IgemmArgs a, long long M) {
   using gemm4x::BM;
   using namespace gemm8p;
@@ -1194,8 +1018,8 @@ __global__ __launch_bounds__(512, 2) void gemm8p_kernel(const IgemmArgs a, long 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   __builtin_assume(wave >= 0 && wave < 8);
-  const int hi = lane >> 5, l31 = lane & 31;
-  const int q4 = lane >> 4, l15 = lane & 15;                  // kM16: fragment row / 16-byte K chunk of the 16 x 16 x 32 shape
+  const int hi = lane >> 5, l31 = lane & 31;                  // lane roles of round 3's 32 x 32 x 16 phases: see PINNED below
+  const int q4 = lane >> 4, l15 = lane & 15;                  // fragment row / 16-byte K chunk of the 16 x 16 x 32 shape
   const int grp = wave >> 2, wc = wave & 3;                   // token half = phase group, 64-channel slab
 
   G4Const kc;
@@ -1235,7 +1059,10 @@ __global__ __launch_bounds__(512, 2) void gemm8p_kernel(const IgemmArgs a, long 
       __builtin_amdgcn_raw_ptr_buffer_load_lds(srd_w, (lds_ptr_t)(smem + WB + buf * OPB + wave * 4096 + jj * 1024), 16, voff[jj], soff, 0, 0);
   };
 
-  // fragment addresses: one per (K-32 half, K-16 slice) and operand; row blocks (+32 rows: same swizzle) and the buffer are immediates
+  // PINNED: the fragment addresses of round 3's 32 x 32 x 16 phases (git history).  Nothing reads them, but the empty asm that once kept them
+  // in registers makes the compiler compute them - eight VALU results per wave, once per workgroup.  Deleting the block deletes those
+  // instructions and shifts the register allocation of the whole kernel (tools/isa_equal.py against 728c3f6), so it stays until a change
+  // that is allowed to move instructions and is measured on the GPU.
   int aoff[2][2], boff[2][2];
   {
     const int ra = grp * 128 + l31, rb = wc * 64 + l31;
@@ -1249,9 +1076,7 @@ __global__ __launch_bounds__(512, 2) void gemm8p_kernel(const IgemmArgs a, long 
         asm volatile("" : "+v"(aoff[h][kk]), "+v"(boff[h][kk]));
       }
   }
-  f32x16 acc[2][4];
-  bf16x8 xf[4][2], wf[2][2];
-  // kM16: one address per K-32 half and operand (row l15 of a 16-row block, chunk 4 h + q4 of the 128-B row; +16 rows keep the swizzle's
+  // fragment addresses: one per K-32 half and operand (row l15 of a 16-row block, chunk 4 h + q4 of the 128-B row; +16 rows keep the swizzle's
   // (row >> 1) & 7 term, so the blocks are immediates), token block pb = 16 rows, channel block ib = 16 rows of the wave's slab
   int aoff16[2], boff16[2];
   {
@@ -1260,7 +1085,7 @@ __global__ __launch_bounds__(512, 2) void gemm8p_kernel(const IgemmArgs a, long 
     for (int h = 0; h < 2; ++h) {
       aoff16[h] = XB + ra * ROWB + (((h * 4 + q4) ^ ((ra >> 1) & 7)) << 4);
       boff16[h] = WB + rb * ROWB + (((h * 4 + q4) ^ ((rb >> 1) & 7)) << 4);
-      if (kM16) asm volatile("" : "+v"(aoff16[h]), "+v"(boff16[h]));
+      asm volatile("" : "+v"(aoff16[h]), "+v"(boff16[h]));
     }
   }
   f32x4 acc16[4][8];                                          // [channel block][token block]; lane: token l15, channels 4 q4 .. 4 q4 + 3
@@ -1281,81 +1106,45 @@ __global__ __launch_bounds__(512, 2) void gemm8p_kernel(const IgemmArgs a, long 
     __builtin_amdgcn_sched_barrier(0);
   }
 
-  unsigned long long tm_lb = 0, tm_mb = 0;
   // phase u of a chunk: K-64 step u >> 1 (= its buffer), K-32 half u & 1
   auto step = [&](auto uc, bool hold) {
     constexpr int u = decltype(uc)::value;
     constexpr int buf = u >> 1, h = u & 1;
     // ---- LOAD ----
-    if (kM16) {
 #pragma unroll
-      for (int pb = 0; pb < 8; ++pb) x16[pb] = *(const bf16x8*)(smem + aoff16[h] + buf * OPB + pb * (16 * ROWB));
+    for (int pb = 0; pb < 8; ++pb) x16[pb] = *(const bf16x8*)(smem + aoff16[h] + buf * OPB + pb * (16 * ROWB));
 #pragma unroll
-      for (int ib = 0; ib < 4; ++ib) w16[ib] = *(const bf16x8*)(smem + boff16[h] + buf * OPB + ib * (16 * ROWB));
-    } else {
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk) {
-#pragma unroll
-        for (int p = 0; p < 4; ++p) xf[p][kk] = *(const bf16x8*)(smem + aoff[h][kk] + buf * OPB + p * (32 * ROWB));
-#pragma unroll
-        for (int i = 0; i < 2; ++i) wf[i][kk] = *(const bf16x8*)(smem + boff[h][kk] + buf * OPB + i * (32 * ROWB));
-      }
-    }
+    for (int ib = 0; ib < 4; ++ib) w16[ib] = *(const bf16x8*)(smem + boff16[h] + buf * OPB + ib * (16 * ROWB));
     if (u == 0) stage(std::integral_constant<int, 1>{}, ca_base, ca_nrec, cw_base, cw_nrec, c_soff + ROWB);   // step 1 of this chunk
     if (u == 2) stage(std::integral_constant<int, 0>{}, na_base, na_nrec, nw_base, nw_nrec, n_soff);          // step 0 of the next one
     __builtin_amdgcn_sched_barrier(0);
     if (h == 1 && grp) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    unsigned long long tq = 0;
-    if (kTiming) { tq = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); }
     __builtin_amdgcn_s_barrier();
-    if (kTiming) { tm_lb += __builtin_amdgcn_s_memtime() - tq; }
     __builtin_amdgcn_sched_barrier(0);
     // ---- MFMA ----
     __builtin_amdgcn_s_setprio(1);                            // (with / without: 0.825 / 0.824 ms - kept for the hand-over at the barrier)
-    if (kM16) {
 #pragma unroll
-      for (int ib = 0; ib < 4; ++ib)
+    for (int ib = 0; ib < 4; ++ib)
 #pragma unroll
-        for (int pb = 0; pb < 8; ++pb) acc16[ib][pb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w16[ib], x16[pb], acc16[ib][pb], 0, 0, 0);
-    } else {
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int p = 0; p < 4; ++p) acc[i][p] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[i][kk], xf[p][kk], acc[i][p], 0, 0, 0);
-    }
+      for (int pb = 0; pb < 8; ++pb) acc16[ib][pb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w16[ib], x16[pb], acc16[ib][pb], 0, 0, 0);
     __builtin_amdgcn_s_setprio(0);
     __builtin_amdgcn_sched_barrier(0);
     if (h == 1 && !grp) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (u == 3 && hold) return;                               // waves 4-7, last phase of a tile: epilogue first, then this barrier
-    if (kTiming) { tq = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); }
     __builtin_amdgcn_s_barrier();
-    if (kTiming) { tm_mb += __builtin_amdgcn_s_memtime() - tq; }
     __builtin_amdgcn_sched_barrier(0);
   };
 
   // epilogue-side lane role: 4 lanes x 8 columns cover the 32 columns (64 B) one accumulator block holds of an output row
   const int e_px = lane >> 2, e_ch = lane & 3;
-  unsigned long long tm_walk = 0, tm_epi = 0, tm_n = 0, tm0 = 0, tm1 = 0;
   for (int tile = (int)blockIdx.x; tile < ntiles; tile += G) {
-    if (kTiming) tm0 = __builtin_amdgcn_s_memtime();
     const G4Tile c = g4_decode(kc, tile);
     const int col0 = c.n0 + wc * 64;
-    if (kM16) {
 #pragma unroll
-      for (int ib = 0; ib < 4; ++ib)
+    for (int ib = 0; ib < 4; ++ib)
 #pragma unroll
-        for (int pb = 0; pb < 8; ++pb) acc16[ib][pb] = f32x4{0.f, 0.f, 0.f, 0.f};
-    } else {
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int p = 0; p < 4; ++p)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[i][p][r] = 0.f;
-    }
+      for (int pb = 0; pb < 8; ++pb) acc16[ib][pb] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     for (int kq = 0; kq < nk4; ++kq) {
       step(std::integral_constant<int, 0>{}, false);
@@ -1371,7 +1160,6 @@ __global__ __launch_bounds__(512, 2) void gemm8p_kernel(const IgemmArgs a, long 
       __builtin_amdgcn_sched_barrier(0);
     }
 
-    if (kTiming) tm1 = __builtin_amdgcn_s_memtime();
     // bias / gate rows of the lane's 16 channels: loaded HERE, not before the K walk - 48 registers the walk does not have (2 waves per SIMD);
     // they land under the first accumulator block's trip through LDS
     asm volatile("" ::: "memory");
@@ -1418,24 +1206,13 @@ __global__ __launch_bounds__(512, 2) void gemm8p_kernel(const IgemmArgs a, long 
 #pragma unroll
               for (int it = 0; it < 2; ++it) rr[it] = __builtin_amdgcn_raw_buffer_load_b128(srd_r, (int)r_off[it], h * 64, 0);
             }
-            if (kM16) {                                              // the block's 32 tokens x 32 channels = 2 x 2 quads of 16 x 16
 #pragma unroll
-              for (int dj = 0; dj < 2; ++dj)
+            for (int dj = 0; dj < 2; ++dj)                           // the block's 32 tokens x 32 channels = 2 x 2 quads of 16 x 16
 #pragma unroll
-                for (int di = 0; di < 2; ++di) {
-                  const int row = dj * 16 + l15, ch = di * 4 + q4;
-                  *(f32x4*)(eslice + row * 128 + ((ch ^ (row & 7)) << 4)) = acc16[2 * h + di][2 * p + dj];
-                }
-            } else {
-#pragma unroll
-              for (int gq = 0; gq < 4; ++gq) {
-                f32x4 o;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) o[e] = acc[h][p][gq * 4 + e];
-                const int ch = 2 * gq + hi;                            // 16-B chunk of the 128-B row
-                *(f32x4*)(eslice + l31 * 128 + ((ch ^ (l31 & 7)) << 4)) = o;
+              for (int di = 0; di < 2; ++di) {
+                const int row = dj * 16 + l15, ch = di * 4 + q4;     // ch: 16-B chunk of the 128-B row
+                *(f32x4*)(eslice + row * 128 + ((ch ^ (row & 7)) << 4)) = acc16[2 * h + di][2 * p + dj];
               }
-            }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");         // wave-private slice: no barrier needed
             f32x4 lo[2], hi4[2];
 #pragma unroll
@@ -1472,7 +1249,7 @@ __global__ __launch_bounds__(512, 2) void gemm8p_kernel(const IgemmArgs a, long 
               const u32x4 v = {pack_bf2(x0[0], x0[1]), pack_bf2(x0[2], x0[3]), pack_bf2(x1[0], x1[1]), pack_bf2(x1[2], x1[3])};
               if (a.nt_out) __builtin_amdgcn_raw_buffer_store_b128(v, srd_o, (int)o_off[it], h * 64, 2);   // aux 2 = nt
               else __builtin_amdgcn_raw_buffer_store_b128(v, srd_o, (int)o_off[it], h * 64, 0);
-              __builtin_amdgcn_sched_barrier(0);                       // store-data hazard: see gemm4x
+              __builtin_amdgcn_sched_barrier(0);                       // store-data hazard: see conv3x3_halo4x_kernel
               asm volatile("s_nop 3" ::: "memory");
               __builtin_amdgcn_sched_barrier(0);
             }
@@ -1485,16 +1262,11 @@ __global__ __launch_bounds__(512, 2) void gemm8p_kernel(const IgemmArgs a, long 
     // the counted-vmcnt scheme of the K walk restarts from an empty queue (stores count in vmcnt on gfx9)
     __builtin_amdgcn_s_waitcnt(0x0F70);                       // vmcnt(0), as a builtin: the compiler's own wait tracking sees the queue empty
     asm volatile("" ::: "memory");
-    if (kTiming) { const unsigned long long tm2 = __builtin_amdgcn_s_memtime(); tm_walk += tm1 - tm0; tm_epi += tm2 - tm1; ++tm_n; }
     if (grp) {                                                // the barrier held back above
       __builtin_amdgcn_sched_barrier(0);
       __builtin_amdgcn_s_barrier();
       __builtin_amdgcn_sched_barrier(0);
     }
-  }
-  if (kTiming && a.zero && blockIdx.x == 100 && lane == 0) {     // TIMING build: `zero` carries the host's debug buffer
-    unsigned long long* o = (unsigned long long*)a.zero + wave * 8;
-    o[0] = tm_walk; o[1] = tm_lb; o[2] = tm_mb; o[3] = tm_epi; o[4] = tm_n; o[5] = (unsigned long long)nk4 * 4;
   }
   if (!grp) {                                                 // balance the second group's extra first barrier
     __builtin_amdgcn_sched_barrier(0);
@@ -1663,12 +1435,6 @@ static int cu_count() {
     (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
     if (dev >= 0 && dev < DOVE_MAX_DEVICES) cus[dev].store(n, std::memory_order_relaxed);
   }
-#ifdef DOVE_TIMING_BUILD
-  {
-    const char* e = getenv("DOVE_CU_LIMIT");                  // tools/archive/cumask_probe.py: persistent grids sized for a CU-masked stream
-    if (e && atoi(e) > 0 && atoi(e) < n) return atoi(e);
-  }
-#endif
   return n;
 }
 
@@ -1709,12 +1475,6 @@ extern "C" int dove_conv_partial_launches(const dove_conv_desc* d) {
 }
 
 static int conv_dispatch(const dove_conv_desc* d, void* stream, ConvKernel kern);
-#ifdef DOVE_TIMING_BUILD
-static bool halo_m16() {                                       // DOVE_HALO_M16=0 selects the predecessor walk; read per call (the A/B tool toggles it)
-  const char* e = getenv("DOVE_HALO_M16");
-  return !(e && atoi(e) == 0);
-}
-#endif
 
 // GEMM tail: ntiles 256x256 tiles on G persistent workgroups take ceil(ntiles / G) rounds, and the last round of the DiT's
 // N = 3072 GEMMs (864 tiles on 256 CUs) keeps 96 CUs busy for a whole tile time.  When the rows behind the last FULL round fit
@@ -1766,7 +1526,7 @@ extern "C" int dove_conv_igemm_bf16(const dove_conv_desc* d, void* stream) {
   DOVE_CHECK_ARG(!d->out_f32 || (kern0 == K_IGEMM_FAST && !d->resid && d->act == 0),
                  "conv_igemm: out_f32 is only implemented for plain convs that dispatch to igemm_fast_kernel");
   long long rows_main = 0;
-  if (kern0 == K_GEMM8P && !DOVE_DBG_BUF && gemm_tail_split(d, &rows_main)) {
+  if (kern0 == K_GEMM8P && gemm_tail_split(d, &rows_main)) {
     dove_conv_desc m = *d, t = *d;
     m.w_in = m.w_out = (int)rows_main;
     const long long tail = (long long)d->w_out - rows_main;
@@ -1778,11 +1538,7 @@ extern "C" int dove_conv_igemm_bf16(const dove_conv_desc* d, void* stream) {
     const int rc = conv_dispatch(&m, stream, K_GEMM8P);
     return rc ? rc : conv_dispatch(&t, stream, K_IGEMM_FAST);
   }
-  const int rc = conv_dispatch(d, stream, kern0);
-#ifdef DOVE_TIMING_BUILD
-  g_timing_debug_buf = nullptr;     // one call only
-#endif
-  return rc;
+  return conv_dispatch(d, stream, kern0);
 }
 
 static int conv_dispatch(const dove_conv_desc* d, void* stream, ConvKernel kern) {
@@ -1805,13 +1561,7 @@ static int conv_dispatch(const dove_conv_desc* d, void* stream, ConvKernel kern)
   a.sub = 0;
   a.out_f32 = d->out_f32;
   a.nt_out = 0;
-  a.debug = 0;
-#ifdef DOVE_TIMING_BUILD
-  {
-    const char* e = getenv("DOVE_IGEMM_ABLATE");          // read per call: the A/B tools toggle it
-    a.debug = e ? atoi(e) : 0;
-  }
-#endif
+  a.reserved = 0;
   hipStream_t s = (hipStream_t)stream;
   const long long M = (long long)nb * d->t_out * d->h_out * d->w_out;
   switch (kern) {
@@ -1822,70 +1572,20 @@ static int conv_dispatch(const dove_conv_desc* d, void* stream, ConvKernel kern)
       // outputs of out / ff2 1.0-1.5 % slower.  Inside the operator the consumers then read from HBM what the cache might have kept: the
       // whole clip gains 0.1-0.25 % (within-run, three A/Bs; profiles/r03_gemm8p_nt.log) - kept because it never loses, not because it matters
       a.nt_out = (long long)M * d->ldo * 2 > (256ll << 20);
-#ifdef DOVE_TIMING_BUILD
-      if (a.debug & 8) a.nt_out = 1;                             // tools/archive/gemm8p_nt.py: force on / off
-      if (a.debug & 16) a.nt_out = 0;
-#endif
       const long long nt = ((M + gemm4x::BM - 1) / gemm4x::BM) * a.tiles_n;
       DOVE_CHECK_ARG(nt > 0 && nt < (1ll << 31), "conv_igemm: grid too large");
       DOVE_CHECK_ARG(!(d->gate && d->act), "conv_igemm: gate with activation is not a path of the reference");
       const int cus = cu_count();
       const unsigned grid4 = nt > cus ? (unsigned)cus : (unsigned)nt;
-#ifdef DOVE_TIMING_BUILD
-      {
-        // the predecessor kernel, for within-run A/Bs: DOVE_GEMM8P=0 (read per call: tools/archive/gemm8p_ab.py toggles it), with DOVE_GEMM4X_SCHED=0
-        // its round-2 DMA order (tools/archive/gemm4x_sched.py); a debug buffer selects the s_memtime instantiations (tools/gemm*_timing.py)
-        const char* e8 = getenv("DOVE_GEMM8P");
-        if (e8 && atoi(e8) == 0) {
-          const char* es = getenv("DOVE_GEMM4X_SCHED");
-          int variant = 0;
-          if (DOVE_DBG_BUF && d->act == 0 && !d->gate) { a.zero = (const bf16_t*)DOVE_DBG_BUF; variant = 3; }
-          else if (es && atoi(es) == 0 && !d->gate && d->act == 0) variant = 4;
-          else if (d->gate) variant = 2;
-          else if (d->act == 1) variant = 1;
-          return launch_gemm4x_timing(a, M, grid4, variant, s);
-        }
-        {
-          const char* em = getenv("DOVE_GEMM_M16");               // tools/archive/gemm_m16_ab.py: DOVE_GEMM_M16=0 = the 32 x 32 x 16 phases of round 3, read per call
-          if (em && atoi(em) == 0 && !DOVE_DBG_BUF) {
-            static PerDeviceOnce attr8m;
-            if (auto once_ = attr8m.guard()) {
-              (void)hipFuncSetAttribute((const void*)gemm8p_kernel<false, false, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, gemm8p::LDS_BYTES);
-              (void)hipFuncSetAttribute((const void*)gemm8p_kernel<true, false, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, gemm8p::LDS_BYTES);
-              (void)hipFuncSetAttribute((const void*)gemm8p_kernel<false, true, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, gemm8p::LDS_BYTES);
-            }
-            if (d->gate) hipLaunchKernelGGL((gemm8p_kernel<false, true, false, false>), dim3(grid4), dim3(512), gemm8p::LDS_BYTES, s, a, M);
-            else if (d->act == 1) hipLaunchKernelGGL((gemm8p_kernel<true, false, false, false>), dim3(grid4), dim3(512), gemm8p::LDS_BYTES, s, a, M);
-            else hipLaunchKernelGGL((gemm8p_kernel<false, false, false, false>), dim3(grid4), dim3(512), gemm8p::LDS_BYTES, s, a, M);
-            DOVE_CHECK_LAUNCH("dove_conv_igemm_bf16(gemm8p 32x32x16)");
-            return DOVE_OK;
-          }
-        }
-        if (DOVE_DBG_BUF) {
-          static PerDeviceOnce attr8t;
-          if (auto once_ = attr8t.guard()) {
-            (void)hipFuncSetAttribute((const void*)gemm8p_kernel<false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, gemm8p::LDS_BYTES);
-            (void)hipFuncSetAttribute((const void*)gemm8p_kernel<true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, gemm8p::LDS_BYTES);
-            (void)hipFuncSetAttribute((const void*)gemm8p_kernel<false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, gemm8p::LDS_BYTES);
-          }
-          a.zero = (const bf16_t*)DOVE_DBG_BUF;
-          if (d->gate) hipLaunchKernelGGL((gemm8p_kernel<false, true, true>), dim3(grid4), dim3(512), gemm8p::LDS_BYTES, s, a, M);
-          else if (d->act == 1) hipLaunchKernelGGL((gemm8p_kernel<true, false, true>), dim3(grid4), dim3(512), gemm8p::LDS_BYTES, s, a, M);
-          else hipLaunchKernelGGL((gemm8p_kernel<false, false, true>), dim3(grid4), dim3(512), gemm8p::LDS_BYTES, s, a, M);
-          DOVE_CHECK_LAUNCH("dove_conv_igemm_bf16(gemm8p timing)");
-          return DOVE_OK;
-        }
-      }
-#endif
       static PerDeviceOnce attr8;
       if (auto once_ = attr8.guard()) {
-        (void)hipFuncSetAttribute((const void*)gemm8p_kernel<false, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, gemm8p::LDS_BYTES);
-        (void)hipFuncSetAttribute((const void*)gemm8p_kernel<true, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, gemm8p::LDS_BYTES);
-        (void)hipFuncSetAttribute((const void*)gemm8p_kernel<false, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, gemm8p::LDS_BYTES);
+        (void)hipFuncSetAttribute((const void*)gemm8p_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, gemm8p::LDS_BYTES);
+        (void)hipFuncSetAttribute((const void*)gemm8p_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, gemm8p::LDS_BYTES);
+        (void)hipFuncSetAttribute((const void*)gemm8p_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, gemm8p::LDS_BYTES);
       }
-      if (d->gate) hipLaunchKernelGGL((gemm8p_kernel<false, true, false, true>), dim3(grid4), dim3(512), gemm8p::LDS_BYTES, s, a, M);
-      else if (d->act == 1) hipLaunchKernelGGL((gemm8p_kernel<true, false, false, true>), dim3(grid4), dim3(512), gemm8p::LDS_BYTES, s, a, M);
-      else hipLaunchKernelGGL((gemm8p_kernel<false, false, false, true>), dim3(grid4), dim3(512), gemm8p::LDS_BYTES, s, a, M);
+      if (d->gate) hipLaunchKernelGGL((gemm8p_kernel<false, true>), dim3(grid4), dim3(512), gemm8p::LDS_BYTES, s, a, M);
+      else if (d->act == 1) hipLaunchKernelGGL((gemm8p_kernel<true, false>), dim3(grid4), dim3(512), gemm8p::LDS_BYTES, s, a, M);
+      else hipLaunchKernelGGL((gemm8p_kernel<false, false>), dim3(grid4), dim3(512), gemm8p::LDS_BYTES, s, a, M);
       DOVE_CHECK_LAUNCH("dove_conv_igemm_bf16(gemm8p)");
       return DOVE_OK;
     }
@@ -1908,17 +1608,10 @@ static int conv_dispatch(const dove_conv_desc* d, void* stream, ConvKernel kern)
       const long long g4 = (long long)a.T_out * a.tiles_h * a.tiles_w * a.tiles_n;
       DOVE_CHECK_ARG(g4 > 0 && g4 < (1ll << 31), "conv_igemm: grid too large");
       static PerDeviceOnce attrs;
-      if (auto once_ = attrs.guard()) (void)hipFuncSetAttribute((const void*)(conv3x3_halo4x_kernel<false, false, true, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, Halo4xCfg::LDS_BYTES);
+      if (auto once_ = attrs.guard()) (void)hipFuncSetAttribute((const void*)(conv3x3_halo4x_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, Halo4xCfg::LDS_BYTES);
       const int cus = cu_count();
       const unsigned grid = g4 > cus ? (unsigned)cus : (unsigned)g4;
-#ifdef DOVE_TIMING_BUILD
-      if (!halo_m16()) {                                         // tools/archive/halo_m16_ab.py, DOVE_HALO_M16=0: the 32 x 32 x 16 walk of rounds 1-4
-        static PerDeviceOnce attrm;
-        if (auto once_ = attrm.guard()) (void)hipFuncSetAttribute((const void*)(conv3x3_halo4x_kernel<false, false, true, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, Halo4xCfg::LDS_BYTES);
-        hipLaunchKernelGGL((conv3x3_halo4x_kernel<false, false, true, true, false>), dim3(grid), dim3(256), Halo4xCfg::LDS_BYTES, s, a);
-      } else
-#endif
-      hipLaunchKernelGGL((conv3x3_halo4x_kernel<false, false, true, true, true>), dim3(grid), dim3(256), Halo4xCfg::LDS_BYTES, s, a);
+      hipLaunchKernelGGL((conv3x3_halo4x_kernel<false, true>), dim3(grid), dim3(256), Halo4xCfg::LDS_BYTES, s, a);
       DOVE_CHECK_LAUNCH("dove_conv_igemm_bf16(halo4x sub-pixel)");
       return DOVE_OK;
     }
@@ -1936,44 +1629,13 @@ static int conv_dispatch(const dove_conv_desc* d, void* stream, ConvKernel kern)
       DOVE_CHECK_ARG(g4 > 0 && g4 < (1ll << 31), "conv_igemm: grid too large");
       static PerDeviceOnce attr4;
       if (auto once_ = attr4.guard()) {
-        (void)hipFuncSetAttribute((const void*)(conv3x3_halo4x_kernel<false, false, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, Halo4xCfg::LDS_BYTES);
-        (void)hipFuncSetAttribute((const void*)(conv3x3_halo4x_kernel<false, false, true, false, true, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, H4Geo<1>::LDS_BYTES);
-        (void)hipFuncSetAttribute((const void*)(conv3x3_halo4x_kernel<true, false, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, Halo4xCfg::LDS_BYTES);
-#ifdef DOVE_TIMING_BUILD
-        (void)hipFuncSetAttribute((const void*)conv3x3_halo4x_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, Halo4xCfg::LDS_BYTES);
-#endif
+        (void)hipFuncSetAttribute((const void*)(conv3x3_halo4x_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, Halo4xCfg::LDS_BYTES);
+        (void)hipFuncSetAttribute((const void*)(conv3x3_halo4x_kernel<false, false, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, H4Geo<1>::LDS_BYTES);
+        (void)hipFuncSetAttribute((const void*)(conv3x3_halo4x_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, Halo4xCfg::LDS_BYTES);
       }
       const int cus = cu_count();                              // persistent: one workgroup per CU walks its share of the tiles
       const unsigned grid = g4 > cus ? (unsigned)cus : (unsigned)g4;
-#ifdef DOVE_TIMING_BUILD
-      if (DOVE_DBG_BUF && kern == K_HALO4X) {                   // tools/archive/halo4x_timing.py
-        a.gate = (const float*)DOVE_DBG_BUF;
-        static PerDeviceOnce attrt;
-        if (auto once_ = attrt.guard())
-          (void)hipFuncSetAttribute((const void*)(conv3x3_halo4x_kernel<false, true, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, Halo4xCfg::LDS_BYTES);
-        if (halo_m16()) hipLaunchKernelGGL((conv3x3_halo4x_kernel<false, true, true, false, true>), dim3(grid), dim3(256), Halo4xCfg::LDS_BYTES, s, a);
-        else hipLaunchKernelGGL((conv3x3_halo4x_kernel<false, true>), dim3(grid), dim3(256), Halo4xCfg::LDS_BYTES, s, a);
-      } else
-#endif
-#ifdef DOVE_TIMING_BUILD
-      if (!halo_m16()) {                                         // tools/archive/halo_m16_ab.py, DOVE_HALO_M16=0: the 32 x 32 x 16 walk of rounds 1-4
-        static PerDeviceOnce attrm;
-        if (auto once_ = attrm.guard()) {
-          (void)hipFuncSetAttribute((const void*)(conv3x3_halo4x_kernel<false, false, true, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, Halo4xCfg::LDS_BYTES);
-          (void)hipFuncSetAttribute((const void*)(conv3x3_halo4x_kernel<true, false, true, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, Halo4xCfg::LDS_BYTES);
-        }
-        if (kern == K_HALO4X_UP) hipLaunchKernelGGL((conv3x3_halo4x_kernel<true, false, true, false, false>), dim3(grid), dim3(256), Halo4xCfg::LDS_BYTES, s, a);
-        else hipLaunchKernelGGL((conv3x3_halo4x_kernel<false, false, true, false, false>), dim3(grid), dim3(256), Halo4xCfg::LDS_BYTES, s, a);
-      } else
-#endif
-#ifdef DOVE_TIMING_BUILD
-      if ((a.debug & 64) && kern == K_HALO4X) {                  // tools/e2e_env_ab.py DOVE_IGEMM_ABLATE 64 0: epilogue without the early slice write
-        static PerDeviceOnce attrp;
-        if (auto once_ = attrp.guard()) (void)hipFuncSetAttribute((const void*)(conv3x3_halo4x_kernel<false, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, Halo4xCfg::LDS_BYTES);
-        hipLaunchKernelGGL((conv3x3_halo4x_kernel<false, false, false>), dim3(grid), dim3(256), Halo4xCfg::LDS_BYTES, s, a);
-      } else
-#endif
-      if (kern == K_HALO4X_UP) hipLaunchKernelGGL((conv3x3_halo4x_kernel<true, false, true, false, true>), dim3(grid), dim3(256), Halo4xCfg::LDS_BYTES, s, a);
+      if (kern == K_HALO4X_UP) hipLaunchKernelGGL((conv3x3_halo4x_kernel<true>), dim3(grid), dim3(256), Halo4xCfg::LDS_BYTES, s, a);
       else {
         // a partial last tile column goes to a launch of its own in 32 x 16 tiles when that saves a round: see halo4x_plan
         const bool wpart = halo4x_plan(d);
@@ -1984,21 +1646,9 @@ static int conv_dispatch(const dove_conv_desc* d, void* stream, ConvKernel kern)
           b.ty0 = 0; b.nty = nty; b.tx0 = tx0; b.ntx = ntx; b.h_lim = d->h_out; b.w_lim = w_lim;
           const long long g = (long long)b.T_out * nty * ntx * b.tiles_n;
           const unsigned gr = g > cus ? (unsigned)cus : (unsigned)g;
-          if (part == 0) hipLaunchKernelGGL((conv3x3_halo4x_kernel<false, false, true, false, true, 0>), dim3(gr), dim3(256), H4Geo<0>::LDS_BYTES, s, b);
-          else hipLaunchKernelGGL((conv3x3_halo4x_kernel<false, false, true, false, true, 1>), dim3(gr), dim3(256), H4Geo<1>::LDS_BYTES, s, b);
+          if (part == 0) hipLaunchKernelGGL((conv3x3_halo4x_kernel<false, false, 0>), dim3(gr), dim3(256), H4Geo<0>::LDS_BYTES, s, b);
+          else hipLaunchKernelGGL((conv3x3_halo4x_kernel<false, false, 1>), dim3(gr), dim3(256), H4Geo<1>::LDS_BYTES, s, b);
         };
-#ifdef DOVE_TIMING_BUILD
-        if (const char* e = getenv("DOVE_HALO_FILL"); e && atoi(e) == 1) {     // tools/gn_fusion_cost.py: the product walk + the fusion's instruction mix
-          static PerDeviceOnce attrf;
-          if (auto once_ = attrf.guard())
-            (void)hipFuncSetAttribute((const void*)(conv3x3_halo4x_kernel<false, false, true, false, true, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, H4Geo<0>::LDS_BYTES);
-          IgemmArgs b = a;
-          b.ty0 = 0; b.nty = a.tiles_h; b.tx0 = 0; b.ntx = a.tiles_w; b.h_lim = d->h_out; b.w_lim = d->w_out;
-          hipLaunchKernelGGL((conv3x3_halo4x_kernel<false, false, true, false, true, 0, true>), dim3(grid), dim3(256), H4Geo<0>::LDS_BYTES, s, b);
-          DOVE_CHECK_LAUNCH("dove_conv_igemm_bf16(halo4x, kFill)");
-          return DOVE_OK;
-        }
-#endif
         launch(0, a.tiles_h, 0, cols_main, wm);
         if (wpart) launch(1, (d->h_out + 31) / 32, cols_main, 1, d->w_out);
       }

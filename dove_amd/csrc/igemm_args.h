@@ -1,5 +1,5 @@
 // Shared pieces of the implicit-GEMM translation units (igemm.hip: the product kernels and the dispatch; igemm_legacy.hip: the generic
-// v1 kernel that only test-sized upsample-fused convs reach; gemm4x_timing.hip: round 2's GEMM, TIMING build only).
+// v1 kernel that only test-sized upsample-fused convs reach).
 #pragma once
 #include <stdlib.h>
 
@@ -7,24 +7,6 @@
 
 #include "common.h"
 #include "../../include/dove_hip.h"
-
-// tools/*_timing.py hand a device buffer to the NEXT conv call (per-phase s_memtime logs / ablation operands).  It used to be a field
-// of dove_conv_desc; the product struct no longer carries it - the hook exists in libdove_hip_timing.so only.
-#ifdef DOVE_TIMING_BUILD
-extern void* g_timing_debug_buf;                     // defined in igemm.hip (with dove_timing_set_debug_buf)
-#define DOVE_DBG_BUF g_timing_debug_buf
-#else
-#define DOVE_DBG_BUF ((void*)nullptr)
-#endif
-
-// Work-skipping ablation switches and s_memtime phase logs exist ONLY in a -DDOVE_TIMING_BUILD library (built by the
-// tools/*_timing.py helpers into a separate file); in the product build DOVE_DBG() is the constant 0, the branches fold
-// away, no timing instantiation is emitted and no environment variable can make a kernel skip work.
-#ifdef DOVE_TIMING_BUILD
-#define DOVE_DBG(a) ((a).debug)
-#else
-#define DOVE_DBG(a) 0
-#endif
 
 struct IgemmArgs {
   const bf16_t* x;
@@ -42,7 +24,8 @@ struct IgemmArgs {
   long long ldo, ldr;
   long long gate_split;
   int tw_log2, tiles_w, tiles_h, tiles_n;
-  int debug;  // -DDOVE_TIMING_BUILD only (tools/, never the product library): 1 skip A loads, 2 skip B loads, 4 skip MFMA
+  int reserved;        // always 0.  The slot (once the ablation word of a retired timing build) stays: dropping it moves the kernarg offset of every
+                       // field below and, with the offsets, the register allocation of 13 of igemm.hip's 14 kernels (tools/isa_equal.py)
   float* gn_partial;   // conv3x3_halo4x only: fused GroupNorm(32) partial sums of the stored output, [rows][32][2]
   int cpg_log;         // log2(channels per group) = log2(Cout / 32)
   int out_f32;         // igemm_fast only: `out` is float [..][ldo] (no bf16 rounding): the tap-split conv_out's partial sums
@@ -87,12 +70,11 @@ __device__ __forceinline__ const bf16_t* igemm_src_frame(const IgemmArgs& a, int
 
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
+// Tile and persistent supertile walk of the plain GEMM (gemm8p_kernel; gemm_tail_split sizes its row split by BM).  The names gemm4x / g4_* are
+// historical: round 2's gemm4x_kernel introduced the walk and is gone, gemm8p_kernel kept it unchanged.
 namespace gemm4x {
-constexpr int BM = 256, BN = 256, BK = 32, ROWB = 64;
-constexpr int A_ST = BM * ROWB, ST = A_ST + BN * ROWB;      // 16384 + 16384 per stage
-constexpr int NST = 4;
-constexpr int EPI = NST * ST;                                // epilogue staging: 4 waves x 32 rows x 256 B (XOR-swizzled)
-constexpr int LDS_BYTES = EPI + 4 * 8192;                    // 163840 = all of a CU's LDS
+constexpr int BM = 256, BN = 256;                            // workgroup tile
+constexpr int ROWB = 64;                                     // bytes of K per K-32 step: G4State.soff advances by four of them per chunk
 }  // namespace gemm4x
 struct G4Tile { int m0, n0; };
 struct G4Const { int ntiles, G, tiles_n, nk4, K; long long M; };
@@ -140,8 +122,3 @@ __device__ __forceinline__ void g4_advance(G4State& s, const IgemmArgs& a, const
 
 // generic v1 kernel (igemm_legacy.hip): BN in {32, 64, 128}, BK = 64 if Cin % 64 == 0 else 32
 int launch_igemm_legacy(const IgemmArgs& a, unsigned grid, int BN, bool bk64, hipStream_t s);
-#ifdef DOVE_TIMING_BUILD
-// round 2's one-wave-per-SIMD GEMM (gemm4x_timing.hip), for the within-run A/Bs of tools/archive/gemm8p_ab.py / gemm4x_sched.py / gemm4x_timing.py:
-// variant 0 plain, 1 GELU, 2 gate, 3 s_memtime log (a.zero = debug buffer), 4 round-2 DMA order
-int launch_gemm4x_timing(const IgemmArgs& a, long long M, unsigned grid, int variant, hipStream_t s);
-#endif

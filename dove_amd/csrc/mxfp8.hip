@@ -16,7 +16,7 @@
 // lane (row = l & 31, h = l >> 5) supplies the scale of elements [64 s + 32 h, 64 s + 32 h + 32) of its row at step
 // s = 4c + u and selects byte u with op_sel - one coalesced dword load per fragment row per 256 K.
 //
-// GEMM structure = gemm4x of igemm.hip (256 x 256 tile, ONE wave per SIMD with the 512-register file, 4-stage LDS ring
+// GEMM structure = round 2's bf16 gemm4x_kernel (igemm.hip's GEMM before gemm8p; git history.  256 x 256 tile, ONE wave per SIMD with the 512-register file, 4-stage LDS ring
 // filled by 16-byte LDS-DMA three steps ahead with counted vmcnt, persistent workgroups, XCD-aware rasterisation,
 // LDS-transposed full-line epilogue) with 64-BYTE K rows holding 64 fp8 elements: one 32x32x64 MFMA (131 kFLOP) replaces
 // two 32x32x16 bf16 MFMAs per (i, p) pair, so a K-step carries the same 8 LDS-DMA + 16 fragment reads but twice the
@@ -119,7 +119,7 @@ struct MxState {
 };
 __device__ __forceinline__ MxTile mx_decode(const MxConst& k, int id) {
   const unsigned rest = xcd_remap((unsigned)(id < k.ntiles ? id : k.ntiles - 1), (unsigned)k.ntiles);
-  const unsigned GM = k.tiles_n > 16 ? 8u : 1u;              // same rasterisation as gemm4x (igemm.hip g4_decode)
+  const unsigned GM = k.tiles_n > 16 ? 8u : 1u;              // same rasterisation as the bf16 GEMM (igemm_args.h g4_decode)
   const unsigned tiles_m = (unsigned)(k.ntiles / k.tiles_n);
   const unsigned per_group = GM * (unsigned)k.tiles_n;
   const unsigned group = rest / per_group, within = rest - group * per_group;
@@ -448,7 +448,7 @@ __global__ __launch_bounds__(256, 1) void gemm_mxfp8_kernel(const MxArgs a) {
               }
               const u32x4 v = {pack_bf2(x0[0], x0[1]), pack_bf2(x0[2], x0[3]), pack_bf2(x1[0], x1[1]), pack_bf2(x1[2], x1[3])};
               __builtin_amdgcn_raw_buffer_store_b128(v, srd_o, (int)o_off[it], h * 128, 0);
-              // store-data hazard (see gemm4x): keep the data registers untouched for a few cycles after the 16-B store
+              // store-data hazard (see conv3x3_halo4x_kernel in igemm.hip): keep the data registers untouched for a few cycles after the 16-B store
               __builtin_amdgcn_sched_barrier(0);
               asm volatile("s_nop 3" ::: "memory");
               __builtin_amdgcn_sched_barrier(0);

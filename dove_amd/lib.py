@@ -175,18 +175,6 @@ def kernel_source_sha256() -> str:
     return h.hexdigest()
 
 
-def use_timing_build():
-    """tools/ only: bind the separate -DDOVE_TIMING_BUILD library (ablation switches, s_memtime phase logs; built by
-    ``dove_amd/csrc/build.sh timing``) instead of the product library.  Must be called before the first ``load()``."""
-    global LIB_PATH
-    assert _lib is None, "use_timing_build() must precede the first load()"
-    path = os.path.join(_HERE, "libdove_hip_timing.so")
-    if not os.path.exists(path):
-        import subprocess
-        subprocess.check_call(["bash", os.path.join(_HERE, "csrc", "build.sh"), "timing"])
-    LIB_PATH = path
-
-
 def load():
     """Load libdove_hip.so (built by ``__graft_entry__.build()`` / dove_amd/csrc/build.sh)."""
     global _lib

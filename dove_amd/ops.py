@@ -149,7 +149,7 @@ def conv_kernel_name(x_shape, pc: PackedConv, *, stride=1, pad=(None, None), up=
 def conv(x: torch.Tensor, pc: PackedConv, *, cache: torch.Tensor | None = None, stride: int = 1, pad=(None, None),
          up: int = 0, tmode: int = 0, t_out: int | None = None, hw_out=None, resid: torch.Tensor | None = None,
          gate: torch.Tensor | None = None, gate_split: int = 0, act: int = 0, ldo: int | None = None,
-         out: torch.Tensor | None = None, debug_buf: torch.Tensor | None = None,
+         out: torch.Tensor | None = None,
          gn_eps: float | None = None, out_f32: bool = False, nb: int = 1, tdup: int = 0, weight_sums: bool = True) -> torch.Tensor:
     """Implicit-GEMM conv on channels-last x [T,H,W,cin_pad] -> [t_out,h_out,w_out,ldo].
 
@@ -216,8 +216,6 @@ def conv(x: torch.Tensor, pc: PackedConv, *, cache: torch.Tensor | None = None, 
     d.ldo = ldo
     d.ldr = resid.shape[-1] if resid is not None else 0
     d.gate_split = gate_split
-    if debug_buf is not None:      # tools/*_timing.py only: exists in libdove_hip_timing.so, an AttributeError on the product library
-        L.load().dove_timing_set_debug_buf(C.c_void_p(debug_buf.data_ptr()))
     d.out_f32 = int(out_f32)
     if resid is not None:
         assert resid.dtype == torch.bfloat16 and resid.numel() == nb * t_out * hw_out[0] * hw_out[1] * resid.shape[-1]

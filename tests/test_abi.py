@@ -53,7 +53,7 @@ def test_conv_desc_struct_size_is_checked(lib):
     assert lib.dove_conv_kernel_name(C.byref(d)) == b"" and int(lib.dove_conv_gn_partial_rows(C.byref(d))) == 0
     d.struct_size = 0
     assert lib.dove_conv_igemm_bf16(C.byref(d), None) == -1
-    assert not hasattr(L.ConvDesc, "debug_buf") and not hasattr(lib, "dove_timing_set_debug_buf")      # timing hook: timing library only
+    assert not hasattr(L.ConvDesc, "debug_buf") and not hasattr(lib, "dove_timing_set_debug_buf")      # the retired timing library's hook
 
 
 def test_dispatch_rule_mirror(lib):
@@ -128,13 +128,23 @@ def test_graft_entry_build_version_check(lib):
 
 
 def test_product_library_has_no_work_skipping_switches():
-    """ablation switches (skip A/B loads, skip MFMA) and s_memtime timing instantiations live only in the
-    separate -DDOVE_TIMING_BUILD library; the product .so must not even contain the environment variable's name."""
+    """no environment variable can make a kernel skip work or select another kernel.  The ablation switches (skip A/B loads,
+    skip MFMA), the kernel-variant switches and the s_memtime timing instantiations used to live in a second, -D...TIMING_BUILD library
+    built from the same sources; that build mode is gone (git history has it and its tools), so the one library must not contain any of the
+    switches' names and the sources must not carry the second mode."""
+    import glob
     import os
     from dove_amd import lib as L
     blob = open(L.LIB_PATH, "rb").read()
-    assert b"DOVE_IGEMM_ABLATE" not in blob
+    for var in ("DOVE_IGEMM_ABLATE", "DOVE_GEMM8P", "DOVE_GEMM4X_SCHED", "DOVE_GEMM_M16", "DOVE_HALO_M16", "DOVE_HALO_FILL", "DOVE_CU_LIMIT",
+                "DOVE_ATTN_BOUND", "DOVE_ATTN_PIPE"):
+        assert var.encode() not in blob, var
     assert not os.path.basename(L.LIB_PATH).endswith("_timing.so")
+    pkg = os.path.dirname(L.__file__)
+    macro = "DOVE_" + "TIMING_BUILD"
+    for fn in glob.glob(os.path.join(pkg, "**", "*"), recursive=True):
+        if os.path.isfile(fn) and fn.endswith((".py", ".sh", ".hip", ".h")):
+            assert macro not in open(fn, errors="replace").read(), fn
 
 
 def test_kernel_dispatch_table():
