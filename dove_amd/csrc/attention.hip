@@ -89,6 +89,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_kernel(const bf16_t* __re
     qb = blockIdx.x;
   }
   const long long q0 = (long long)qb * (NW * 32) + wave * 32;
+  const bool live = q0 + l31 < N;                // rows of the padded tail are never stored - and never vote for a rescale (compute)
   // skip_bounded: attn_pipe_kernel (attention_pipe.hip) ran first on every head with a finite bound and marked the ones it could not finish
   // NaN; this kernel keeps the marked ones and those whose bound was NaN / infinite to begin with.  (Before any load: ~6.9 k workgroups of a
   // DiT attention call leave here.)
@@ -191,7 +192,9 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_kernel(const bf16_t* __re
       mt = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));        // the other half of the same query column
     }
     const bool first = tile == 0;
-    if (first || __any(mt > THR)) {              // wave-uniform and rare after the first tiles
+    // (only rows that exist vote: the vote moves m, and with it the rounding, of every row of the wave whose tile maximum is positive - the
+    // contents of the Q rows [N, Npad) must not reach the stored rows that way.  A pad row's own m may then lag: its lane may overflow, alone.)
+    if (first || __any(live && mt > THR)) {      // wave-uniform and rare after the first tiles
       // everything still expressed against the old max is rescaled exactly once, before this tile's P exists
       const float delta = first ? mt : fmaxf(mt, 0.f);
       const float alpha = first ? 1.f : __builtin_amdgcn_exp2f(-delta);   // first tile: O = l = 0, and 2^(-mt) may overflow

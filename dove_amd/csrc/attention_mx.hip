@@ -198,6 +198,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_mx_kernel(const unsigned 
     qb = blockIdx.x;
   }
   const long long q0 = (long long)qb * (NW * 32) + wave * 32;
+  const bool live = q0 + l31 < N;                // rows of the padded tail are never stored - and never vote for a rescale (as attention.hip)
 
   v8i qf;
   {
@@ -279,7 +280,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_mx_kernel(const unsigned 
       mt = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
     }
     const bool first = tile == 0;
-    if (first || __any(mt > THR)) {
+    if (first || __any(live && mt > THR)) {
       const float delta = first ? mt : fmaxf(mt, 0.f);
       const float alpha = first ? 1.f : __builtin_amdgcn_exp2f(-delta);
       m += delta;
