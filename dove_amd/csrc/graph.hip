@@ -25,6 +25,7 @@
 
 #include "common.h"
 #include "../../include/dove_hip.h"
+#include "ctx_access.h"
 
 namespace {
 
@@ -1155,6 +1156,10 @@ extern "C" int dove_create(int device, const dove_model_config* cfg, dove_ctx** 
   *out = c;
   return DOVE_OK;
 }
+// csrc/ctx_access.h: what the whole-video session (csrc/video.hip) reads of a context
+const dove_model_config* dove_ctx_config(const dove_ctx* c) { return c && c->finalized ? &c->cfg : nullptr; }
+int dove_ctx_nranks(const dove_ctx* c) { return c ? c->nranks : 0; }
+int dove_ctx_device(const dove_ctx* c) { return c ? c->device : 0; }
 extern "C" void dove_comm_destroy(dove_ctx* c);
 extern "C" void dove_destroy(dove_ctx* c) {
   if (!c) return;
@@ -1684,6 +1689,8 @@ static int ensure_ws(dove_ctx* c, int F, int H, int W) {
   if (!c->arena.base || (c->arena.owned && c->arena.cap < want && c->arena.live.empty())) CHK(dove_set_workspace(c, nullptr, want));
   return 0;
 }
+
+int dove_ctx_reserve(dove_ctx* c, int F, int H, int W) { return ensure_ws(c, F, H, W); }
 
 // ---- two-stream frame-batch loop (dove_ctx::opt_vae_streams) ----
 struct VaeStreams {

@@ -190,3 +190,118 @@ class GraphContext:
                                       int(timestep), sqrt_alpha, sqrt_one_minus_alpha, C.byref(aux) if aux is not None else None,
                                       C.byref(pre) if pre is not None else None, L.ptr(out), L.BF16, L.stream_ptr()), "dove_sr_clip")
         return out
+
+
+class VideoSession:
+    """The streaming whole-video session of the graph level (include/dove_hip.h ``dove_video_*``): what
+    ``stream.sr_stream`` does - plan, noise, SR per piece, stitch, colour fix, conversion - inside the library, on device buffers.
+
+    ``in_fmt`` / ``out_fmt``: None = RGB uint8 frames [n,H,W,3], or a ``yuv.YuvFormat`` = Y4M frame payloads [n, frame_bytes].
+    ``text``: the prompt embedding [L, text_dim] (moved to the device as bfloat16).  ``sqrt_alpha`` / ``sqrt_one_minus_alpha``: the
+    scheduler's coefficients at ``timestep`` (``scheduler._coeffs``); ``noise_step`` = (n, sqrt_alpha_n, sqrt_one_minus_alpha_n) or None.
+    ``aux(T, h, w) -> (rope, timestep_proj)``: optional host tables per piece shape, as the ``rope`` / ``timestep_proj`` of ``sr_clip``.
+    ``max_frames``: with ``chunk_len == 0`` (one piece of the whole clip) the most frames that will be pushed."""
+
+    def __init__(self, ctx: GraphContext, width: int, height: int, text: torch.Tensor, timestep: int, sqrt_alpha: float,
+                 sqrt_one_minus_alpha: float, *, upscale: int = 4, chunk_len: int = 0, overlap_t: int = 8, tile_size_hw=(0, 0),
+                 overlap_hw=(32, 32), color_fix: str | None = None, in_fmt=None, out_fmt=None, noise_step=None, seed: int = 0,
+                 max_frames: int = 0, max_push: int = 0, aux=None):
+        from . import colorfix
+        self.ctx, self._h = ctx, C.c_void_p()
+        self._text = text.to(ctx.device, dtype=torch.bfloat16).contiguous()
+        if self._text.dim() == 3:
+            self._text = self._text[0].contiguous()
+        p = L.VideoParams()
+        p.width, p.height, p.upscale = width, height, upscale
+        p.chunk_len, p.overlap_t = chunk_len, overlap_t
+        p.tile_h, p.tile_w = tile_size_hw
+        p.overlap_h, p.overlap_w = overlap_hw
+        if color_fix is not None and color_fix not in colorfix.MODES:
+            raise ValueError(f"color_fix must be one of {sorted(colorfix.MODES)} or None, got {color_fix!r}")
+        p.color_fix = colorfix.MODES[color_fix] if color_fix else 0
+        p.in_format, p.out_format = (L.VIDEO_YUV if in_fmt is not None else L.VIDEO_RGB_U8), (L.VIDEO_YUV if out_fmt is not None else L.VIDEO_RGB_U8)
+        if in_fmt is not None:
+            p.in_yuv = in_fmt._c(True)
+        if out_fmt is not None:
+            p.out_yuv = out_fmt._c(False)
+        p.text, p.text_len = self._text.data_ptr(), self._text.shape[0]
+        p.timestep, p.sqrt_alpha, p.sqrt_one_minus_alpha = int(timestep), sqrt_alpha, sqrt_one_minus_alpha
+        if noise_step:
+            p.noise_step, p.noise_sqrt_alpha, p.noise_sqrt_one_minus_alpha = int(noise_step[0]), noise_step[1], noise_step[2]
+        p.seed, p.max_frames, p.max_push = int(seed), int(max_frames), int(max_push)
+        self._aux_keep = {}
+        if aux is not None:
+            def fill(user, T, h, w, out):
+                try:
+                    key = (T, h, w)
+                    if key not in self._aux_keep:                 # the tables live as long as the session: the step's work is asynchronous
+                        rope, tp = aux(T, h, w)
+                        self._aux_keep[key] = GraphContext._aux(rope, tp)
+                    a = self._aux_keep[key][0]
+                    if a is not None:                             # (None, None): the library's own tables for this shape
+                        out[0].rope_cos, out[0].rope_sin, out[0].timestep_proj = a.rope_cos, a.rope_sin, a.timestep_proj
+                    return 0
+                except Exception:                                # noqa: BLE001 - no exception crosses the C boundary
+                    return -1
+            self._aux_cb = L.VIDEO_AUX_FN(fill)
+            p.aux_fn = self._aux_cb
+        self.params = p
+        with torch.cuda.device(ctx.device):
+            L.check(L.load().dove_video_open(ctx._h, C.byref(p), C.byref(self._h)), "dove_video_open")
+        fin, fout, ho, wo, mx = C.c_size_t(), C.c_size_t(), C.c_int(), C.c_int(), C.c_int()
+        L.check(L.load().dove_video_info(self._h, C.byref(fin), C.byref(fout), C.byref(ho), C.byref(wo), C.byref(mx)), "dove_video_info")
+        self.in_frame_bytes, self.out_frame_bytes, self.out_height, self.out_width, self.max_step_frames = fin.value, fout.value, ho.value, wo.value, mx.value
+        self.rgb_out = out_fmt is None
+        self.done = False
+
+    def workspace_bytes(self) -> int:
+        """Bytes of the session's one device allocation (the pieces themselves run in the context's arena)."""
+        return int(L.load().dove_video_workspace_bytes(self.ctx._h, C.byref(self.params)))
+
+    def push(self, frames: torch.Tensor):
+        """``frames``: uint8 on the device, [n,H,W,3] RGB or [n, frame_bytes] payloads."""
+        L.require_cuda(frames)
+        n = frames.shape[0]
+        if frames.dtype != torch.uint8 or (n and frames.numel() != n * self.in_frame_bytes):
+            raise ValueError(f"push: {tuple(frames.shape)} {frames.dtype} is not uint8 with {self.in_frame_bytes} bytes per frame")
+        L.check(L.load().dove_video_push(self._h, L.ptr(frames), n, L.stream_ptr()), "dove_video_push")
+
+    def end(self):
+        L.check(L.load().dove_video_end_of_input(self._h), "dove_video_end_of_input")
+
+    def need(self):
+        """Input frames still missing before ``step`` can run (0: it can); None when only the end of the input will do (chunk_len 0)."""
+        n, e = C.c_longlong(), C.c_int()
+        L.check(L.load().dove_video_need(self._h, C.byref(n), C.byref(e)), "dove_video_need")
+        return None if e.value else int(n.value)
+
+    def step(self, out: torch.Tensor | None = None) -> torch.Tensor:
+        """Run one temporal chunk; returns its final frames - uint8 [k,Ho,Wo,3] or [k, frame_bytes], a view of ``out`` (allocated for
+        ``max_step_frames`` frames when not given).  ``self.done`` is set after the last chunk."""
+        if out is None:
+            shape = (self.max_step_frames, self.out_height, self.out_width, 3) if self.rgb_out else (self.max_step_frames, self.out_frame_bytes)
+            out = torch.empty(shape, dtype=torch.uint8, device=self.ctx.device)
+        L.require_cuda(out)
+        k, done = C.c_int(), C.c_int()
+        L.check(L.load().dove_video_step(self._h, L.ptr(out), out.numel() * out.element_size(), C.byref(k), C.byref(done), L.stream_ptr()),
+                "dove_video_step")
+        self.done = bool(done.value)
+        flat = out.reshape(-1)[:k.value * self.out_frame_bytes]
+        return flat.view(k.value, self.out_height, self.out_width, 3) if self.rgb_out else flat.view(k.value, self.out_frame_bytes)
+
+    def close(self):
+        if self._h:
+            L.load().dove_video_close(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -16,6 +16,7 @@ METRIC_PSNR, METRIC_SSIM, METRIC_RGB_TO_Y = 1, 2, 4           # dove_fr_metrics 
 COLORFIX_WAVELET, COLORFIX_ADAIN, COLORFIX_CLAMP = 1, 2, 1    # dove_color_fix modes / flag
 YUV_444, YUV_422, YUV_420, YUV_MONO = 0, 1, 2, 3              # dove_yuv_format.chroma
 YUV_SITING_LEFT, YUV_SITING_CENTRE = 0, 1                     # dove_yuv_format.siting_h
+VIDEO_RGB_U8, VIDEO_YUV = 0, 1                                # dove_video_params.in_format / out_format
 
 
 class ConvDesc(C.Structure):
@@ -66,6 +67,27 @@ class DitAux(C.Structure):
     _fields_ = [("rope_cos", C.c_void_p), ("rope_sin", C.c_void_p), ("timestep_proj", C.c_void_p)]
 
 
+VIDEO_AUX_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(DitAux))   # dove_video_aux_fn
+
+
+class VideoParams(C.Structure):
+    """dove_video_params (include/dove_hip.h): one whole-video session.  ``struct_size`` is filled in on construction, like ConvDesc."""
+    _fields_ = [("struct_size", C.c_uint), ("reserved", C.c_uint),
+                ("width", C.c_int), ("height", C.c_int), ("upscale", C.c_int),
+                ("chunk_len", C.c_int), ("overlap_t", C.c_int), ("tile_h", C.c_int), ("tile_w", C.c_int), ("overlap_h", C.c_int),
+                ("overlap_w", C.c_int), ("color_fix", C.c_int), ("in_format", C.c_int), ("out_format", C.c_int),
+                ("in_yuv", YuvFormat), ("out_yuv", YuvFormat),
+                ("text", C.c_void_p), ("text_len", C.c_int), ("timestep", C.c_int),
+                ("sqrt_alpha", C.c_float), ("sqrt_one_minus_alpha", C.c_float),
+                ("noise_step", C.c_int), ("noise_sqrt_alpha", C.c_float), ("noise_sqrt_one_minus_alpha", C.c_float),
+                ("max_frames", C.c_int), ("max_push", C.c_int), ("seed", C.c_ulonglong),
+                ("aux_fn", VIDEO_AUX_FN), ("aux_user", C.c_void_p)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size = C.sizeof(VideoParams)
+
+
 class PreNoise(C.Structure):
     """dove_pre_noise: `--noise_step` of the graph-level dove_sr_clip."""
     _fields_ = [("eps", C.c_void_p), ("eps_dtype", C.c_int), ("sqrt_alpha", C.c_float), ("sqrt_one_minus_alpha", C.c_float)]
@@ -77,6 +99,7 @@ STAT_HALO_PREPOSTED, STAT_HALO_BLOCKING, STAT_HALO_SENT, STAT_HALO_COMMUNICATORS
 
 
 _VP, _I, _LL, _F = C.c_void_p, C.c_int, C.c_longlong, C.c_float
+_ULL, _PI, _PLL = C.c_ulonglong, C.POINTER(C.c_int), C.POINTER(C.c_longlong)
 XFER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p)   # dove_xfer_fn
 GROUP_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p)                                  # dove_group_fn
 
@@ -139,6 +162,25 @@ SIGNATURES = {
                        C.c_size_t, _VP],
     "dove_rgb_to_yuv_u8": [C.POINTER(ImageView), _I, _I, _I, C.POINTER(YuvFormat), _VP, _VP],
     "dove_yuv_to_rgb_u8": [_VP, _I, _I, _I, C.POINTER(YuvFormat), _VP, _VP],
+    # whole videos from C: the host planner returns counts (>= 0) where it fills a list, so its restype is the same int
+    "dove_plan_padding": [_I, _I, _I, _PI, _PI, _PI],
+    "dove_plan_output_size": [_I, _I, _I, _PI, _PI],
+    "dove_plan_temporal_chunks": [_I, _I, _I, _PI, _I],
+    "dove_plan_spatial_tiles": [_I, _I, _I, _I, _I, _I, _PI, _I],
+    "dove_plan_valid_region": [_PI, _I, _I, _I, _I, _I, _I, _PI, _PI],
+    "dove_plan_pieces": [_I, _I, _I, _I, _I, _I, _I, _I, _I, _PI, _PI, _PI, _I],
+    "dove_plan_check_coverage": [_PI, _I, _I, _I, _I],
+    "dove_chunk_planner_create": [_I, _I, C.POINTER(_VP)],
+    "dove_chunk_planner_next": [_VP, _LL, _I, _PLL, _PLL, _PI],
+    "dove_philox_u32": [_VP, _LL, _ULL, _ULL, _ULL, _VP],
+    "dove_randn": [_VP, _I, _LL, _ULL, _ULL, _ULL, _VP],
+    "dove_stitch": [_VP, _I, _I, _I, _PI, _VP, _I, _I, _I, _I, _I, _I, _VP],
+    "dove_video_open": [_VP, C.POINTER(VideoParams), C.POINTER(_VP)],
+    "dove_video_info": [_VP, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), _PI, _PI, _PI],
+    "dove_video_push": [_VP, _VP, _I, _VP],
+    "dove_video_end_of_input": [_VP],
+    "dove_video_need": [_VP, _PLL, _PI],
+    "dove_video_step": [_VP, _VP, C.c_size_t, _PI, _PI, _VP],
 }
 PLAIN = {"dove_last_error": (C.c_char_p, []), "dove_abi_version": (C.c_int, []), "dove_comm_destroy": (None, [C.c_void_p]),
          "dove_conv_gn_partial_rows": (C.c_longlong, [C.POINTER(ConvDesc)]),
@@ -155,7 +197,11 @@ PLAIN = {"dove_last_error": (C.c_char_p, []), "dove_abi_version": (C.c_int, []),
          "dove_workspace_high_water": (C.c_size_t, [_VP]),
          "dove_fr_metrics_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
          "dove_color_fix_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I]),
-         "dove_yuv_frame_bytes": (C.c_size_t, [_I, _I, _I])}
+         "dove_yuv_frame_bytes": (C.c_size_t, [_I, _I, _I]),
+         "dove_chunk_planner_need": (C.c_longlong, [_VP]),
+         "dove_chunk_planner_destroy": (None, [_VP]),
+         "dove_video_workspace_bytes": (C.c_size_t, [_VP, C.POINTER(VideoParams)]),
+         "dove_video_close": (None, [_VP])}
 
 
 def kernel_source_sha256() -> str:

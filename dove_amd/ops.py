@@ -720,6 +720,37 @@ def yuv_to_rgb_u8(payload: torch.Tensor, h: int, w: int, fmt: L.YuvFormat) -> to
     return out
 
 
+def randn(shape, seed: int, stream_id: int = 0, dtype=torch.float32, offset: int = 0, device="cuda") -> torch.Tensor:
+    """Standard normals of the library's counter-based generator (csrc/video.hip ``dove_randn``: Philox4x32-10 keyed by ``seed``, counter
+    (element / 4, ``stream_id``), Box-Muller; tests/randn_ref.py is the definition): the elements [offset, offset + numel) of stream
+    (seed, stream_id), row-major in ``shape``.  float32, or bfloat16 = the RNE rounding of the float32 value.  The same bits on every call,
+    whatever the launch geometry or the split over calls - and the same a C host draws, which torch's generator cannot offer."""
+    out = torch.empty(shape, dtype=dtype, device=device)
+    L.require_cuda(out)
+    L.check(L.load().dove_randn(L.ptr(out), L.dt_code(out), out.numel(), int(seed), int(stream_id), int(offset), L.stream_ptr()), "dove_randn")
+    return out
+
+
+def philox_u32(n: int, seed: int, stream_id: int = 0, offset: int = 0, device="cuda") -> torch.Tensor:
+    """The raw Philox4x32-10 words behind ``randn``: the uint32 elements [offset, offset + n) of stream (seed, stream_id), as int64."""
+    out = torch.empty(int(n), dtype=torch.int32, device=device)
+    L.require_cuda(out)
+    L.check(L.load().dove_philox_u32(L.ptr(out), out.numel(), int(seed), int(stream_id), int(offset), L.stream_ptr()), "dove_philox_u32")
+    return out.to(torch.int64) & 0xFFFFFFFF
+
+
+def stitch(chunk: torch.Tensor, piece: torch.Tensor, region: dict) -> torch.Tensor:
+    """``tiling.stitch`` without the write counts (csrc/video.hip ``dove_stitch``): the valid box of ``piece`` [3,f,h,w] goes to its place in
+    ``chunk`` [3,F,H,W]; both bfloat16 and contiguous, ``region`` a dict of ``tiling.get_valid_tile_region``."""
+    L.require_cuda(chunk, piece)
+    if chunk.dtype != torch.bfloat16 or piece.dtype != torch.bfloat16 or chunk.dim() != 4 or piece.dim() != 4 or chunk.shape[0] != 3 or piece.shape[0] != 3:
+        raise ValueError(f"stitch: chunk {tuple(chunk.shape)} {chunk.dtype} and piece {tuple(piece.shape)} {piece.dtype} must be bfloat16 [3,F,H,W]")
+    valid = (C.c_int * 6)(*(region[f"valid_{a}_{e}"] for a in "thw" for e in ("start", "end")))
+    L.check(L.load().dove_stitch(L.ptr(piece), *piece.shape[1:], valid, L.ptr(chunk), *chunk.shape[1:], region["out_t_start"],
+                                 region["out_h_start"], region["out_w_start"], L.stream_ptr()), "dove_stitch")
+    return chunk
+
+
 # ---- MXFP8 linears (BASELINE configs[4]; csrc/mxfp8.hip) ------------------------------------------------------------------
 @dataclass
 class PackedMx:

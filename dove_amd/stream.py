@@ -11,6 +11,10 @@ a lookahead of ``2 * chunk_len - overlap_t`` frames from a chunk's start decides
 be short and is merged, or the clip ends inside it).
 
     ffmpeg -i in.mkv -f yuv4mpegpipe - | python -m dove_amd.stream --input - --output - ... | ffmpeg -i - out.mkv
+
+``--graph`` runs the same stream through the library's whole-video session (``graph.VideoSession``; include/dove_hip.h ``dove_video_*``):
+the reader and writer threads stay, the chunk x tile loop, the noise (``dove_randn`` seeded by ``--seed``), the stitch, the colour fix and
+the conversions run inside libdove_hip.so - what a C host gets from the same calls.
 """
 from __future__ import annotations
 
@@ -290,36 +294,204 @@ def sr_stream(pipe, reader, writer, *, upscale: int = 4, upscale_mode: str = "bi
         failed = True
         raise
     finally:
-        stop.set()
-        while wr.is_alive():                                         # the sentinel goes in even when the queue is full of unwritten items
-            try:
-                out_q.put(None, timeout=_POLL)
-                break
-            except queue.Full:
-                if failed:
-                    try:
-                        out_q.get_nowait()
-                    except queue.Empty:
-                        pass
-        while rd.is_alive():                                         # a reader blocked on a full queue sees `stop` within _POLL
-            try:
-                in_q.get_nowait()
-            except queue.Empty:
-                pass
-            rd.join(_POLL)
-            if failed:
-                break                                                # it may be blocked in read() on a pipe: a daemon thread, not waited for
-        wr.join(join_timeout)
-        rd.join(_POLL if failed else join_timeout)
-        hung = [t.name for t in (rd, wr) if t.is_alive()]
-        if not failed:
-            for t in (wr, rd):
-                if t.error is not None:
-                    raise t.error
-            if hung:
-                raise RuntimeError(f"threads still running after {join_timeout} s: {', '.join(hung)}")
+        _shutdown(stop, rd, wr, in_q, out_q, failed, join_timeout)
     writer.flush()
     return stats
+
+
+def build_graph(args):
+    """The graph-level context the model flags of ``cli.add_model_arguments`` describe -> (GraphContext, empty-prompt embedding,
+    scheduler).  The weights are the ones ``cli.build_pipe`` gives the pipeline (the same checkpoint, or the same seeded random init)."""
+    import os
+
+    from safetensors.torch import load_file
+
+    from . import cli, config, weights
+    from .graph import GraphContext
+    from .scheduler import CogVideoXDPMScheduler
+    cli.check_dtype(args)
+    if args.lora_path:
+        raise ValueError("--graph: --lora_path is fused into the Python pipeline's transformer; fuse it into the checkpoint first")
+    if not os.path.exists(args.prompt_embedding):
+        raise FileNotFoundError(f"empty-prompt embedding not found at {args.prompt_embedding} (the reference ships it; ref :668-676)")
+    emb = load_file(args.prompt_embedding)["prompt_embedding"]
+    if args.random_init or not args.model_path:
+        v, t, s = config.default_configs()
+        if args.num_layers:
+            t["num_layers"] = args.num_layers
+        vsd = weights.LazyStateDict(weights.vae_param_shapes(v), device="cuda")
+        tsd = weights.LazyStateDict(weights.dit_param_shapes(t), device="cuda")
+    else:
+        import json
+        v, vsd = weights.load_component(os.path.join(args.model_path, "vae"), weights.vae_param_shapes)
+        t, tsd = weights.load_component(os.path.join(args.model_path, "transformer"), weights.dit_param_shapes)
+        with open(os.path.join(args.model_path, "scheduler", "scheduler_config.json")) as f:
+            s = {k: val for k, val in json.load(f).items() if not k.startswith("_")}
+    ctx = GraphContext(v, t, vsd, tsd, "cuda")
+    if args.is_vae_st:
+        ctx.enable_tiling()
+    return ctx, emb, CogVideoXDPMScheduler(**dict(s, timestep_spacing="trailing"))
+
+
+@torch.no_grad()
+def sr_stream_graph(ctx, scheduler, reader, writer, text, *, upscale: int = 4, chunk_len: int = 0, overlap_t: int = 8, tile_size_hw=(0, 0),
+                    overlap_hw=(32, 32), noise_step: int = 0, sr_noise_step: int = 399, color_fix: str | None = None, seed: int = 0,
+                    yuv_matrix: str = "bt601", yuv_range: str | None = None, max_frames: int = 256, join_timeout: float = 60.0,
+                    log=_log) -> dict:
+    """``sr_stream`` with the SR loop inside the library: frames from ``reader`` are pushed into a ``graph.VideoSession`` as the planner
+    asks for them, every step's frames leave through ``writer``.  The same reader / writer threads, queues and pinned double buffers.
+    ``max_frames`` bounds the clip only with ``chunk_len == 0`` (one piece of the whole clip, sized when the session opens)."""
+    from .graph import VideoSession
+    dev = ctx.device
+    H, W = reader.height, reader.width
+    is_yuv = hasattr(reader, "chroma")
+    in_fmt = yuvmod.format_of_reader(reader, yuv_matrix, yuv_range) if is_yuv else None
+    out_fmt = yuvmod.YuvFormat(writer.chroma, yuv_matrix, "full" if writer.full_range else "limited")
+    Ho, Wo = output_size(H, W, upscale)
+    if (writer.height, writer.width) != (Ho, Wo):
+        raise ValueError(f"the writer is {writer.width}x{writer.height}; {W}x{H} input at x{upscale} gives {Wo}x{Ho} frames")
+    ov_t = overlap_t if chunk_len > 0 else 0
+    block = max(chunk_len - ov_t, 1) if chunk_len > 0 else 32
+    sa, s1 = scheduler._coeffs(torch.tensor([sr_noise_step]), torch.bfloat16)
+    pre = (noise_step,) + tuple(scheduler._coeffs(torch.tensor([noise_step]), torch.bfloat16)) if noise_step else None
+    if chunk_len == 0:
+        log(f"[dove_amd.stream] --chunk_len 0 is one piece: the whole stream is read before anything is written, and the session is "
+            f"sized for {max_frames} frames (memory grows with the clip; set --chunk_len for bounded memory)")
+    sess = VideoSession(ctx, W, H, text, sr_noise_step, sa, s1, upscale=upscale, chunk_len=chunk_len, overlap_t=overlap_t,
+                        tile_size_hw=tuple(tile_size_hw), overlap_hw=tuple(overlap_hw), color_fix=color_fix, in_fmt=in_fmt, out_fmt=out_fmt,
+                        noise_step=pre, seed=seed, max_frames=max_frames if chunk_len == 0 else 0, max_push=block)
+
+    # the reader / writer threads below are sr_stream's, kept beside it on purpose: sr_stream is pinned byte for byte by its own tests and is
+    # left as it was; only the shutdown (_shutdown) is shared
+    stop = threading.Event()
+    in_q: queue.Queue = queue.Queue(maxsize=2)
+
+    def put(q, item):
+        while not stop.is_set():
+            try:
+                q.put(item, timeout=_POLL)
+                return True
+            except queue.Full:
+                pass
+        return False
+
+    def read_loop():
+        while not stop.is_set():
+            blk = reader.read(block)
+            if blk.shape[0] and not put(in_q, blk):
+                return
+            if blk.shape[0] < block:
+                put(in_q, None)                                     # end of the stream
+                return
+
+    side = torch.cuda.Stream(device=dev)
+    out_q: queue.Queue = queue.Queue(maxsize=2)
+    free_q: queue.Queue = queue.Queue()
+    # a step's device payload lives until its pinned buffer comes round again (two chunks later), like sr_stream's
+    pinned, payloads = [None, None], [None, None]
+    for i in range(2):
+        free_q.put(i)
+
+    def write_loop():
+        while True:
+            item = out_q.get()
+            if item is None:
+                return
+            i, k, event = item
+            event.synchronize()
+            writer.write(pinned[i][:k])
+            free_q.put(i)
+
+    rd, wr = _Worker(read_loop, "dove-stream-reader"), _Worker(write_loop, "dove-stream-writer")
+    stats = {"frames": 0, "chunks": 0, "pieces": 0}
+    total, eof, failed = 0, False, False
+    _, pad_h, pad_w = tiling.match_padding(1, H, W)
+    n_tiles = len(tiling.make_spatial_tiles((H + pad_h) * upscale, (W + pad_w) * upscale, tuple(tile_size_hw),
+                                            tuple(overlap_hw) if tuple(tile_size_hw) != (0, 0) else (0, 0)))
+    rd.start()
+    wr.start()
+    try:
+        while not sess.done:
+            need = sess.need()
+            while not eof and (need is None or need > 0):
+                blk = _get(in_q, rd, "reader")
+                if blk is None:
+                    eof = True
+                    sess.end()
+                    break
+                sess.push(blk.to(dev, non_blocking=True))
+                total += blk.shape[0]
+                need = sess.need()
+            if eof and total == 0:
+                raise ValueError("the input stream holds no frame")
+            i = _get(free_q, wr, "writer")                           # the writer hands a buffer back after its copy has completed
+            if payloads[i] is None:
+                payloads[i] = torch.empty(sess.max_step_frames, sess.out_frame_bytes, dtype=torch.uint8, device=dev)
+            got = sess.step(payloads[i])
+            k = got.shape[0]
+            stats["chunks"] += 1
+            stats["pieces"] += n_tiles
+            if k > 0:
+                if pinned[i] is None or pinned[i].shape[0] < k:
+                    pinned[i] = torch.empty(k, sess.out_frame_bytes, dtype=torch.uint8, pin_memory=True)
+                side.wait_stream(torch.cuda.current_stream(dev))
+                with torch.cuda.stream(side):
+                    pinned[i][:k].copy_(got, non_blocking=True)
+                    event = torch.cuda.Event()
+                    event.record(side)
+                while True:                                          # a full queue stalls this thread, not the GPU
+                    if wr.error is not None:
+                        raise wr.error
+                    try:
+                        out_q.put((i, k, event), timeout=_POLL)
+                        break
+                    except queue.Full:
+                        pass
+                stats["frames"] += k
+            else:
+                free_q.put(i)
+            log(f"[dove_amd.stream] chunk {stats['chunks']}{' (last)' if sess.done else ''}: {stats['frames']} frames written")
+    except BaseException:
+        failed = True
+        raise
+    finally:
+        _shutdown(stop, rd, wr, in_q, out_q, failed, join_timeout)
+        torch.cuda.synchronize(dev)
+        sess.close()
+    writer.flush()
+    return stats
+
+
+def _shutdown(stop, rd, wr, in_q, out_q, failed, join_timeout):
+    """End the reader and writer threads of a streaming run; their errors surface unless the run already failed."""
+    stop.set()
+    while wr.is_alive():                                             # the sentinel goes in even when the queue is full of unwritten items
+        try:
+            out_q.put(None, timeout=_POLL)
+            break
+        except queue.Full:
+            if failed:
+                try:
+                    out_q.get_nowait()
+                except queue.Empty:
+                    pass
+    while rd.is_alive():                                             # a reader blocked on a full queue sees `stop` within _POLL
+        try:
+            in_q.get_nowait()
+        except queue.Empty:
+            pass
+        rd.join(_POLL)
+        if failed:
+            break                                                    # it may be blocked in read() on a pipe: a daemon thread, not waited for
+    wr.join(join_timeout)
+    rd.join(_POLL if failed else join_timeout)
+    hung = [t.name for t in (rd, wr) if t.is_alive()]
+    if not failed:
+        for t in (wr, rd):
+            if t.error is not None:
+                raise t.error
+        if hung:
+            raise RuntimeError(f"threads still running after {join_timeout} s: {', '.join(hung)}")
 
 
 def main(argv=None):
@@ -332,9 +504,17 @@ def main(argv=None):
     ap.add_argument("--input", type=str, required=True, help="a .y4m file, or - for stdin (ffmpeg -f yuv4mpegpipe -)")
     ap.add_argument("--output", type=str, required=True, help="a .y4m file, or - for stdout; then every message goes to stderr")
     ap.add_argument("--prompt", type=str, default="")
+    ap.add_argument("--graph", action="store_true",
+                    help="run the SR loop inside libdove_hip.so (the whole-video session of the graph level, INTEGRATION.md 1e); "
+                         "--seed then seeds the library's own generator (dove_randn), --upscale_mode must be bilinear")
+    ap.add_argument("--max_frames", type=int, default=256, help="--graph with --chunk_len 0: the longest clip the session is sized for")
     cli.add_model_arguments(ap)
     ap.set_defaults(fps=None)                                        # the input's frame rate unless --fps is given
     args = ap.parse_args(argv)
+    if args.graph and args.upscale_mode != "bilinear":
+        ap.error(f"--graph upscales with the library's bilinear kernel; --upscale_mode {args.upscale_mode} needs the Python loop")
+    if args.graph and args.prompt:
+        ap.error("--graph runs the empty prompt (the cached embedding); a prompt needs the Python loop's text encoder")
     to_stdout = args.output == "-"
     sink = None
     if to_stdout:
@@ -345,7 +525,10 @@ def main(argv=None):
         os.dup2(2, 1)
     with contextlib.redirect_stdout(sys.stderr):
         chroma = yuvmod.save_format_to_chroma(args.save_format)
-        pipe, emb = cli.build_pipe(args)
+        if args.graph:
+            ctx, emb, scheduler = build_graph(args)
+        else:
+            pipe, emb = cli.build_pipe(args)
         reader = y4m.Y4MReader(sys.stdin.buffer if args.input == "-" else args.input)
         Ho, Wo = output_size(reader.height, reader.width, args.upscale)
         fps = (args.fps, 1) if args.fps else reader.fps if reader.fps[0] > 0 and reader.fps[1] > 0 else (16, 1)
@@ -353,11 +536,18 @@ def main(argv=None):
         _log(f"[dove_amd.stream] {reader.width}x{reader.height} {reader.tag} -> {Wo}x{Ho} {y4m.WRITE_TAGS[chroma]} "
              f"({args.yuv_matrix}, {args.yuv_range or 'limited'}), {fps[0]}:{fps[1]} fps")
         try:
-            stats = sr_stream(pipe, reader, writer, upscale=args.upscale, upscale_mode=args.upscale_mode, chunk_len=args.chunk_len,
-                              overlap_t=args.overlap_t, tile_size_hw=tuple(args.tile_size_hw), overlap_hw=tuple(args.overlap_hw),
-                              noise_step=args.noise_step, sr_noise_step=args.sr_noise_step, prompt=args.prompt, empty_prompt_embedding=emb,
-                              color_fix=None if args.color_fix == "none" else args.color_fix, yuv_matrix=args.yuv_matrix,
-                              yuv_range=args.yuv_range)
+            if args.graph:
+                stats = sr_stream_graph(ctx, scheduler, reader, writer, emb, upscale=args.upscale, chunk_len=args.chunk_len,
+                                        overlap_t=args.overlap_t, tile_size_hw=tuple(args.tile_size_hw), overlap_hw=tuple(args.overlap_hw),
+                                        noise_step=args.noise_step, sr_noise_step=args.sr_noise_step,
+                                        color_fix=None if args.color_fix == "none" else args.color_fix, seed=args.seed,
+                                        yuv_matrix=args.yuv_matrix, yuv_range=args.yuv_range, max_frames=args.max_frames)
+            else:
+                stats = sr_stream(pipe, reader, writer, upscale=args.upscale, upscale_mode=args.upscale_mode, chunk_len=args.chunk_len,
+                                  overlap_t=args.overlap_t, tile_size_hw=tuple(args.tile_size_hw), overlap_hw=tuple(args.overlap_hw),
+                                  noise_step=args.noise_step, sr_noise_step=args.sr_noise_step, prompt=args.prompt,
+                                  empty_prompt_embedding=emb, color_fix=None if args.color_fix == "none" else args.color_fix,
+                                  yuv_matrix=args.yuv_matrix, yuv_range=args.yuv_range)
         finally:
             reader.close()
             writer.close()

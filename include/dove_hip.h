@@ -515,6 +515,125 @@ int dove_sr_clip(dove_ctx* ctx, const void* video_in, int dtype, int F, int H, i
                  int text_len, int timestep, float sqrt_alpha, float sqrt_one_minus_alpha, const dove_dit_aux* aux,
                  const dove_pre_noise* pre_noise, void* video_out, int out_dtype, void* stream);
 
+/* ---- whole videos from C: the script around process_video (/root/reference/inference_script.py:192-361, :670-731) ----
+ * Host planner: pure host functions (no GPU, no context), the integer logic of dove_amd/tiling.py and dove_amd.stream.ChunkPlanner.  Boxes are
+ * six ints (t0, t1, h0, h1, w0, w1), half-open.  The functions that fill a list return the number of entries (>= 0) and write at most `cap`
+ * of them (a NULL list only counts), or a negative DOVE_E* code with the reference's message in dove_last_error().
+ *   dove_plan_padding:     preprocess_video_match(is_match=True) (ref :220-232): frames -> 8N+1 (repeat the last), H and W -> multiples of 16.
+ *   dove_plan_output_size: (H + pad_h) * upscale - pad_h * 4, likewise W: the reference crops pad * 4 whatever --upscale is (ref :731).
+ *   dove_plan_temporal_chunks: make_temporal_chunks (ref :255-279), chunks [n][2]; chunk_len 0 = one chunk; a short tail is merged into its
+ *     predecessor; "chunk_len must be greater than overlap" otherwise.  A clip of <= overlap_t frames has NO chunk (0 is returned).
+ *   dove_plan_spatial_tiles: make_spatial_tiles (ref :282-329), tiles [n][4] = (h0, h1, w0, w1); a zero tile size = one tile; the last row /
+ *     column is merged; "Tile size must be greater than overlap" otherwise.
+ *   dove_plan_valid_region: get_valid_tile_region (ref :332-361) of `piece` inside a clip of F x H x W: half of each interior overlap is
+ *     dropped.  valid = the kept box in the piece's own coordinates, out = where it lands in the clip.
+ *   dove_plan_pieces: the work list of ref :565-574, :682-683 (dove_amd.tiling.plan), chunk-major and tile-minor, overlaps zeroed on an untiled
+ *     axis (chunk_len 0 / tile size (0, 0)): piece, valid and out boxes [n][6] each (any may be NULL).
+ *   dove_plan_check_coverage: "every voxel written exactly once" (ref :724-729) for n out-boxes [n][6] in a domain of F x H x W, on the
+ *     boxes themselves (no per-voxel counts): a hole fails with "Error: Lack of write in region !!!", else a double write with
+ *     "Error: Write count > 1 in region !!!" - the reference's two messages, in the reference's order.
+ *   dove_chunk_planner_*: make_temporal_chunks one chunk at a time, without the frame count up front.  need: frames that must be known
+ *     (counted from the start of the stream) before next() may be called without eof = start + 2 * chunk_len - overlap_t; -1 for chunk_len 0
+ *     (one chunk of the whole clip: needs the end of the stream).  next(known, eof): returns 1 and the chunk [t0, t1) with last != 0 when it is
+ *     the final one, 0 when no chunk is left (a clip of <= overlap_t frames: none at all), negative when called too early. */
+int dove_plan_padding(int F, int H, int W, int* pad_f, int* pad_h, int* pad_w);
+int dove_plan_output_size(int H, int W, int upscale, int* out_h, int* out_w);
+int dove_plan_temporal_chunks(int F, int chunk_len, int overlap_t, int* chunks, int cap);
+int dove_plan_spatial_tiles(int H, int W, int tile_h, int tile_w, int overlap_h, int overlap_w, int* tiles, int cap);
+int dove_plan_valid_region(const int* piece, int F, int H, int W, int overlap_t, int overlap_h, int overlap_w, int* valid, int* out);
+int dove_plan_pieces(int F, int H, int W, int chunk_len, int overlap_t, int tile_h, int tile_w, int overlap_h, int overlap_w, int* pieces,
+                     int* valid, int* out, int cap);
+int dove_plan_check_coverage(const int* boxes, int n, int F, int H, int W);
+typedef struct dove_chunk_planner dove_chunk_planner;
+int dove_chunk_planner_create(int chunk_len, int overlap_t, dove_chunk_planner** out);
+long long dove_chunk_planner_need(const dove_chunk_planner* p);
+int dove_chunk_planner_next(dove_chunk_planner* p, long long known, int eof, long long* t0, long long* t1, int* last);
+void dove_chunk_planner_destroy(dove_chunk_planner* p);
+
+/* Counter-based normal generator (csrc/video.hip; tests/randn_ref.py is the definition in numpy): what a host without torch's generator
+ * draws the VAE posterior noise from.  Philox4x32-10 (Salmon et al. 2011; multipliers 0xD2511F53, 0xCD9E8D57, key increments 0x9E3779B9,
+ * 0xBB67AE85), key = (seed low, seed high), counter = (block low, block high, stream_id low, stream_id high).  The four output words
+ * x0..x3 of block b are the elements 4b..4b+3 of the stream: element e is word e % 4 of block e / 4.  The call writes the n elements
+ * [offset, offset + n) of stream (seed, stream_id), so any split of a tensor over calls gives the same values.
+ *   dove_philox_u32: the raw words (uint32), exact.
+ *   dove_randn: standard normals by two Box-Muller pairs per block:  u1 = (x0 + 1) 2^-32, u2 = x1 2^-32, r = sqrt(-2 ln u1),
+ *     (z0, z1) = (r cos 2 pi u2, r sin 2 pi u2), and (z2, z3) likewise from (x2, x3).  fp32 arithmetic (u1 above 1/2 goes through
+ *     log1p of the exact complement); INTEGRATION.md 1e gives the measured distance from the fp64 evaluation.  dtype DOVE_F32, or DOVE_BF16 =
+ *     the round-to-nearest-even of that fp32 value.  Deterministic: the bits do not depend on the launch geometry or on the split. */
+int dove_philox_u32(void* out, long long n, unsigned long long seed, unsigned long long stream_id, unsigned long long offset, void* stream);
+int dove_randn(void* out, int dtype, long long n, unsigned long long seed, unsigned long long stream_id, unsigned long long offset,
+               void* stream);
+
+/* The stitch of ref :712-720 for one piece: the box `valid` (piece coordinates) of piece [3][f][h][w] is copied to the box of the same size at
+ * (out_t0, out_h0, out_w0) of chunk [3][f_chunk][Hs][Ws]; both bf16, contiguous.  One launch, no write counts; 16-byte loads and stores when
+ * both boxes allow (the box width, every row / frame / channel stride of both arrays and both box origins multiples of 8 elements, i.e.
+ * 16-byte aligned), 2-byte otherwise.  Nothing outside the box is
+ * written: the chunk buffer needs no clearing when dove_plan_check_coverage has accepted the boxes. */
+int dove_stitch(const void* piece, int f, int h, int w, const int* valid, void* chunk, int f_chunk, int Hs, int Ws, int out_t0, int out_h0,
+                int out_w0, void* stream);
+
+/* The streaming whole-video session: what `python -m dove_amd.stream` does, as push / step calls on device buffers.  The host keeps the
+ * I/O (the library touches no file); the session plans the chunks and tiles, draws the noise, runs dove_sr_clip per piece and stitches,
+ * colour-fixes and converts each chunk's final frames.  Its output is byte-identical to the composition of the operator-level entry points
+ * (tests/test_video_graph_gpu.py).  Bound to a single-rank context (a context with a communicator is refused); the context's options
+ * (VAE tiling, MXFP8, weight sums, VAE streams) apply as they do to dove_sr_clip.  Not thread-safe; one session per context at a time.
+ *   in_format / out_format: DOVE_VIDEO_RGB_U8 = frames [n][H][W][3] u8; DOVE_VIDEO_YUV = Y4M frame payloads of in_yuv / out_yuv
+ *     (dove_yuv_frame_bytes each; in_yuv carries the inverse matrix, out_yuv the forward one).
+ *   upscale: bilinear, dove_preprocess_u8.  color_fix: 0, DOVE_COLORFIX_WAVELET or DOVE_COLORFIX_ADAIN against the upscaled input.
+ *   text [text_len][text_dim] bf16 on the device, borrowed until close.  timestep, sqrt_alpha, sqrt_one_minus_alpha as dove_sr_clip.
+ *   noise_step != 0: the `--noise_step` pre-noising with noise_sqrt_alpha / noise_sqrt_one_minus_alpha (dove_pre_noise).
+ *   seed: piece p (counted over the whole video, chunk-major and tile-minor) draws its posterior noise [L][T][h][w] fp32 as
+ *     dove_randn(seed, stream 2p, offset 0) and its pre-noise eps [T'][L][h][w] fp32 as stream 2p + 1.
+ *   max_frames: chunk_len 0 only (one piece of the whole clip: memory grows with it) - the most frames that will be pushed.
+ *   max_push: the most frames one push adds beyond what dove_video_need asked for (0 = 64); sizes the input ring.
+ *   aux_fn (may be NULL): called on the host before each piece with the DiT's grid - T' latent frames (after the patch_t pad) of h x w
+ *     latents - to fill a dove_dit_aux for that piece (a host that has diffusers' own RoPE tables and timestep projection hands them over, as
+ *     the aux argument of dove_sr_clip; the pointers must stay valid until the step's work has run).  NULL: computed inside the library.
+ * Memory: the pieces run in the context's arena (dove_workspace_bytes of the largest piece); everything else is ONE device allocation of
+ * dove_video_workspace_bytes made at open.  With chunk_len > 0 neither depends on the number of frames pushed.
+ *   push: n frames / payloads in device memory, copied on `stream`; frames no later chunk needs are dropped after each step.
+ *   need: *frames = input frames still missing before dove_video_step can run (0 = it can), *end_of_input = 1 when only the end of the input
+ *     will do (chunk_len 0).  After dove_video_end_of_input both are 0.
+ *   step: runs at most ONE temporal chunk on `stream`: yuv_to_rgb (YUV input) and preprocess; per spatial tile dove_randn, dove_sr_clip and
+ *     dove_stitch; dove_color_fix of the chunk's final frames; dove_postprocess_u8 or dove_rgb_to_yuv_u8 with the padding cropped into `out`.
+ *     *frames_written (known at once: it follows from the plan) frames of dove_video_info's out_frame_bytes each; *done = 1 after the last
+ *     chunk.  out_bytes must hold max_step_frames frames or at least this step's.  A step refused for its arguments, its plan, its
+ *     output size or by aux_fn changes nothing and may be repeated; a launch that fails afterwards ends the session (close it).  Fails with
+ *     the reference's coverage messages when the plan leaves a hole (a clip of <= overlap_t frames has no chunk at all) or writes a voxel
+ *     twice - inside a chunk, or at the seam of two chunks (an odd overlap_t keeps one frame on both sides: "Write count > 1"). */
+#define DOVE_VIDEO_RGB_U8 0
+#define DOVE_VIDEO_YUV 1
+typedef int (*dove_video_aux_fn)(void* user, int T, int h, int w, dove_dit_aux* aux); /* 0 on success */
+typedef struct dove_video_params {
+  unsigned int struct_size; /* = sizeof(dove_video_params) of the caller's header, as dove_conv_desc */
+  unsigned int reserved;    /* 0 */
+  int width, height;        /* of the low-resolution input */
+  int upscale;
+  int chunk_len, overlap_t, tile_h, tile_w, overlap_h, overlap_w;
+  int color_fix;
+  int in_format, out_format;
+  dove_yuv_format in_yuv, out_yuv;
+  const void* text;
+  int text_len;
+  int timestep;
+  float sqrt_alpha, sqrt_one_minus_alpha;
+  int noise_step;
+  float noise_sqrt_alpha, noise_sqrt_one_minus_alpha;
+  int max_frames, max_push;
+  unsigned long long seed;
+  dove_video_aux_fn aux_fn;
+  void* aux_user;
+} dove_video_params;
+typedef struct dove_video dove_video;
+size_t dove_video_workspace_bytes(dove_ctx* ctx, const dove_video_params* params); /* 0: bad parameters (dove_last_error) */
+int dove_video_open(dove_ctx* ctx, const dove_video_params* params, dove_video** out);
+int dove_video_info(const dove_video* v, size_t* in_frame_bytes, size_t* out_frame_bytes, int* out_h, int* out_w, int* max_step_frames);
+int dove_video_push(dove_video* v, const void* frames, int n, void* stream);
+int dove_video_end_of_input(dove_video* v);
+int dove_video_need(const dove_video* v, long long* frames, int* end_of_input);
+int dove_video_step(dove_video* v, void* out, size_t out_bytes, int* frames_written, int* done, void* stream);
+void dove_video_close(dove_video* v);
+
 #ifdef __cplusplus
 }
 #endif
