@@ -17,6 +17,7 @@ COLORFIX_WAVELET, COLORFIX_ADAIN, COLORFIX_CLAMP = 1, 2, 1    # dove_color_fix m
 YUV_444, YUV_422, YUV_420, YUV_MONO = 0, 1, 2, 3              # dove_yuv_format.chroma
 YUV_SITING_LEFT, YUV_SITING_CENTRE = 0, 1                     # dove_yuv_format.siting_h
 VIDEO_RGB_U8, VIDEO_YUV = 0, 1                                # dove_video_params.in_format / out_format
+RESIZE_BILINEAR, RESIZE_BICUBIC, RESIZE_AREA = 0, 1, 2        # dove_resize_f32 modes
 
 
 class ConvDesc(C.Structure):
@@ -174,6 +175,12 @@ SIGNATURES = {
     "dove_chunk_planner_next": [_VP, _LL, _I, _PLL, _PLL, _PI],
     "dove_philox_u32": [_VP, _LL, _ULL, _ULL, _ULL, _VP],
     "dove_randn": [_VP, _I, _LL, _ULL, _ULL, _ULL, _VP],
+    # degradation synthesis: sigma / scale / quality are host arrays
+    "dove_blur2d_f32": [_VP, _I, _I, _I, _VP, _I, _I, _VP, _VP],
+    "dove_resize_f32": [_VP, _I, _I, _I, _I, _I, _I, _VP, _VP],
+    "dove_add_gaussian_noise_f32": [_VP, _I, _I, _I, C.POINTER(C.c_float), _I, _ULL, _ULL, _LL, _VP, _VP],
+    "dove_add_poisson_noise_f32": [_VP, _I, _I, _I, C.POINTER(C.c_float), _I, _ULL, _ULL, _LL, _VP, C.c_size_t, _VP, _VP],
+    "dove_jpeg_roundtrip": [_VP, _I, _I, _I, _PI, _VP, C.c_size_t, _VP, _VP],
     "dove_stitch": [_VP, _I, _I, _I, _PI, _VP, _I, _I, _I, _I, _I, _I, _VP],
     "dove_video_open": [_VP, C.POINTER(VideoParams), C.POINTER(_VP)],
     "dove_video_info": [_VP, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), _PI, _PI, _PI],
@@ -198,6 +205,8 @@ PLAIN = {"dove_last_error": (C.c_char_p, []), "dove_abi_version": (C.c_int, []),
          "dove_fr_metrics_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
          "dove_color_fix_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I]),
          "dove_yuv_frame_bytes": (C.c_size_t, [_I, _I, _I]),
+         "dove_poisson_noise_workspace_bytes": (C.c_size_t, [_I]),
+         "dove_jpeg_roundtrip_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
          "dove_chunk_planner_need": (C.c_longlong, [_VP]),
          "dove_chunk_planner_destroy": (None, [_VP]),
          "dove_video_workspace_bytes": (C.c_size_t, [_VP, C.POINTER(VideoParams)]),

@@ -739,6 +739,80 @@ def philox_u32(n: int, seed: int, stream_id: int = 0, offset: int = 0, device="c
     return out.to(torch.int64) & 0xFFFFFFFF
 
 
+# ---- degradation synthesis (csrc/degrade.hip; tests/degrade_ref.py is the definition) -----------------------------------------------
+def _frames_f32(x: torch.Tensor, what: str):
+    L.require_cuda(x)
+    if x.dtype != torch.float32 or x.dim() != 4 or x.shape[3] != 3:
+        raise ValueError(f"{what}: frames {tuple(x.shape)} {x.dtype} must be float32 [N,H,W,3] (0..255 scale)")
+    return x.shape[0], x.shape[1], x.shape[2]
+
+
+def _per_frame(values, n: int, ctype, what: str):
+    vals = [values] * n if isinstance(values, (int, float)) else list(values)
+    if len(vals) != n:
+        raise ValueError(f"{what}: {len(vals)} per-frame values for {n} frames")
+    return (ctype * n)(*vals)
+
+
+def blur2d(x: torch.Tensor, kernel: torch.Tensor) -> torch.Tensor:
+    """cv2.filter2D(x, -1, kernel) with BORDER_REFLECT_101 on float32 [N,H,W,3] frames: ``kernel`` float32 [k,k] for all frames or
+    [N,k,k] one per frame, k odd in 3..21."""
+    N, H, W = _frames_f32(x, "blur2d")
+    L.require_cuda(kernel)
+    if kernel.dtype != torch.float32 or kernel.dim() not in (2, 3) or kernel.shape[-1] != kernel.shape[-2] or \
+            (kernel.dim() == 3 and kernel.shape[0] != N):
+        raise ValueError(f"blur2d: kernel {tuple(kernel.shape)} {kernel.dtype} must be float32 [k,k] or [{N},k,k]")
+    out = torch.empty_like(x)
+    L.check(L.load().dove_blur2d_f32(L.ptr(x), N, H, W, L.ptr(kernel), kernel.shape[-1], int(kernel.dim() == 3), L.ptr(out), L.stream_ptr()),
+            "dove_blur2d_f32")
+    return out
+
+
+def resize(x: torch.Tensor, oh: int, ow: int, mode: int) -> torch.Tensor:
+    """float32 [N,H,W,3] -> [N,oh,ow,3]; ``mode`` L.RESIZE_BILINEAR / L.RESIZE_BICUBIC (half-pixel centres, A = -0.75, clamped indices) or
+    L.RESIZE_AREA (the pixel-area relation)."""
+    N, H, W = _frames_f32(x, "resize")
+    out = torch.empty(N, int(oh), int(ow), 3, dtype=torch.float32, device=x.device)
+    L.check(L.load().dove_resize_f32(L.ptr(x), N, H, W, int(oh), int(ow), int(mode), L.ptr(out), L.stream_ptr()), "dove_resize_f32")
+    return out
+
+
+def add_gaussian_noise(x: torch.Tensor, sigma, gray: bool, seed: int, stream_id: int = 0, frame0: int = 0) -> torch.Tensor:
+    """x + sigma[n] * z on float32 [N,H,W,3] frames, z from the ``randn`` stream (seed, stream_id) at the index of (frame0 + n, y, x, c) -
+    gray: of (frame0 + n, y, x), one draw per pixel.  ``sigma``: a number or one per frame."""
+    N, H, W = _frames_f32(x, "add_gaussian_noise")
+    out = torch.empty_like(x)
+    L.check(L.load().dove_add_gaussian_noise_f32(L.ptr(x), N, H, W, _per_frame(sigma, N, C.c_float, "add_gaussian_noise"), int(bool(gray)),
+                                                 int(seed), int(stream_id), int(frame0), L.ptr(out), L.stream_ptr()),
+            "dove_add_gaussian_noise_f32")
+    return out
+
+
+def add_poisson_noise(x: torch.Tensor, scale, gray: bool, seed: int, stream_id: int = 0, frame0: int = 0) -> torch.Tensor:
+    """x + scale[n] * (Poisson(v U) / U - v), v = clip(rint(x), 0, 255) (gray: of the luma) and U = 2^ceil(log2(distinct v of the frame));
+    exact sampler on the Philox stream (seed, stream_id).  ``scale``: a number or one per frame."""
+    N, H, W = _frames_f32(x, "add_poisson_noise")
+    lib = L.load()
+    out = torch.empty_like(x)
+    ws = torch.empty(int(lib.dove_poisson_noise_workspace_bytes(N)), dtype=torch.uint8, device=x.device)
+    L.check(lib.dove_add_poisson_noise_f32(L.ptr(x), N, H, W, _per_frame(scale, N, C.c_float, "add_poisson_noise"), int(bool(gray)), int(seed),
+                                           int(stream_id), int(frame0), L.ptr(ws), ws.numel(), L.ptr(out), L.stream_ptr()),
+            "dove_add_poisson_noise_f32")
+    return out
+
+
+def jpeg_roundtrip(x: torch.Tensor, quality) -> torch.Tensor:
+    """float32 [N,H,W,3] -> uint8 [N,H,W,3]: baseline JPEG (4:2:0) at ``quality`` (1..100; a number or one per frame) and back, without
+    the lossless entropy coding."""
+    N, H, W = _frames_f32(x, "jpeg_roundtrip")
+    lib = L.load()
+    out = torch.empty(N, H, W, 3, dtype=torch.uint8, device=x.device)
+    ws = torch.empty(int(lib.dove_jpeg_roundtrip_workspace_bytes(N, H, W)), dtype=torch.uint8, device=x.device)
+    L.check(lib.dove_jpeg_roundtrip(L.ptr(x), N, H, W, _per_frame(quality, N, C.c_int, "jpeg_roundtrip"), L.ptr(ws), ws.numel(), L.ptr(out),
+                                    L.stream_ptr()), "dove_jpeg_roundtrip")
+    return out
+
+
 def stitch(chunk: torch.Tensor, piece: torch.Tensor, region: dict) -> torch.Tensor:
     """``tiling.stitch`` without the write counts (csrc/video.hip ``dove_stitch``): the valid box of ``piece`` [3,f,h,w] goes to its place in
     ``chunk`` [3,F,H,W]; both bfloat16 and contiguous, ``region`` a dict of ``tiling.get_valid_tile_region``."""

@@ -564,6 +564,41 @@ int dove_philox_u32(void* out, long long n, unsigned long long seed, unsigned lo
 int dove_randn(void* out, int dtype, long long n, unsigned long long seed, unsigned long long stream_id, unsigned long long offset,
                void* stream);
 
+/* Degradation synthesis (csrc/degrade.hip; tests/degrade_ref.py is the definition in numpy): the operators of a
+ * RealESRGAN-style low-quality pipeline - blur, resize, Gaussian / Poisson noise, JPEG - on frames x, out [n][h][w][3] fp32, contiguous, in
+ * the 0..255 scale, not clipped between steps.  Every frame on its own; out must not alias x.  Per-frame parameters (sigma, scale, quality)
+ * are HOST arrays of n entries.  Two calls give identical bits, and a clip split over calls gives the bits of one call.
+ *   blur2d: cv2.filter2D(x, -1, kernel): correlation, anchor at the centre, BORDER_REFLECT_101 (dcb|abcd|cba).  kernel: device fp32 [k][k]
+ *     (per_frame 0) or [n][k][k] (per_frame 1), k odd in 3..21; h, w > k / 2.  fp32 FMA, taps in row-major order.
+ *   resize: -> out [n][oh][ow][3].  DOVE_RESIZE_BILINEAR / DOVE_RESIZE_BICUBIC: half-pixel centres, indices clamped at the border, cubic
+ *     A = -0.75 (torch's F.interpolate with align_corners=False, antialias=False; OpenCV's INTER_LINEAR / INTER_CUBIC rule).
+ *     DOVE_RESIZE_AREA: the pixel-area relation - output pixel i is the mean of the source span [i h / oh, (i + 1) h / oh) weighted by
+ *     fractional coverage, separably per axis, enlarging or shrinking.  Source coordinates come from integers.  oh == h and ow == w: a copy.
+ *   add_gaussian_noise: out = x + sigma[i] z, z = the dove_randn stream (seed, stream_id) at the row-major index of
+ *     (frame0 + i, y, x, c) in [.][h][w][3] - gray: of (frame0 + i, y, x) in [.][h][w], one draw for the pixel's three channels.
+ *   add_poisson_noise: per frame v = clip(rint(x), 0, 255) (gray: of 0.299 R + 0.587 G + 0.114 B in fp32, one value per pixel),
+ *     U = 2^ceil(log2(number of distinct v in the frame)), out = x + scale[i] (Poisson(v U) / U - v).  The sampler is exact (inversion below
+ *     rate 10, Hoermann's PTRS from there on, fp64); round r of element e (indexed as for the Gaussian noise) draws its two uniforms from the
+ *     Philox block with counter (e low, e high, stream_id, r), so stream_id < 2^32.  ws: device scratch of
+ *     dove_poisson_noise_workspace_bytes(n) bytes.
+ *   jpeg_roundtrip: -> out [n][h][w][3] u8, what baseline JPEG at quality[i] (1..100) does to trunc(clip(x, 0, 255)): JFIF YCbCr, edge
+ *     replication to whole 16 x 16 MCUs, 4:2:0 chroma (2x2 mean), 8x8 DCT, Annex-K tables under libjpeg's quality rule, dequantisation, IDCT, "fancy"
+ *     3:1 chroma upsampling, RGB.  Integer fixed point throughout: tests/degrade_ref.py fixes every byte.  ws: device scratch of
+ *     dove_jpeg_roundtrip_workspace_bytes(n, h, w) bytes. */
+#define DOVE_RESIZE_BILINEAR 0
+#define DOVE_RESIZE_BICUBIC 1
+#define DOVE_RESIZE_AREA 2
+int dove_blur2d_f32(const float* x, int n, int h, int w, const float* kernel, int k, int per_frame, float* out, void* stream);
+int dove_resize_f32(const float* x, int n, int h, int w, int oh, int ow, int mode, float* out, void* stream);
+int dove_add_gaussian_noise_f32(const float* x, int n, int h, int w, const float* sigma, int gray, unsigned long long seed,
+                                unsigned long long stream_id, long long frame0, float* out, void* stream);
+size_t dove_poisson_noise_workspace_bytes(int n);
+int dove_add_poisson_noise_f32(const float* x, int n, int h, int w, const float* scale, int gray, unsigned long long seed,
+                               unsigned long long stream_id, long long frame0, void* ws, size_t ws_bytes, float* out, void* stream);
+size_t dove_jpeg_roundtrip_workspace_bytes(int n, int h, int w);
+int dove_jpeg_roundtrip(const float* x, int n, int h, int w, const int* quality, void* ws, size_t ws_bytes, unsigned char* out,
+                        void* stream);
+
 /* The stitch of ref :712-720 for one piece: the box `valid` (piece coordinates) of piece [3][f][h][w] is copied to the box of the same size at
  * (out_t0, out_h0, out_w0) of chunk [3][f_chunk][Hs][Ws]; both bf16, contiguous.  One launch, no write counts; 16-byte loads and stores when
  * both boxes allow (the box width, every row / frame / channel stride of both arrays and both box origins multiples of 8 elements, i.e.
