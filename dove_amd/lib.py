@@ -18,6 +18,7 @@ YUV_444, YUV_422, YUV_420, YUV_MONO = 0, 1, 2, 3              # dove_yuv_format.
 YUV_SITING_LEFT, YUV_SITING_CENTRE = 0, 1                     # dove_yuv_format.siting_h
 VIDEO_RGB_U8, VIDEO_YUV = 0, 1                                # dove_video_params.in_format / out_format
 RESIZE_BILINEAR, RESIZE_BICUBIC, RESIZE_AREA = 0, 1, 2        # dove_resize_f32 modes
+ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_TANH = 0, 1, 2, 3        # dove_conv2d_f32 activations
 
 
 class ConvDesc(C.Structure):
@@ -87,6 +88,18 @@ class VideoParams(C.Structure):
     def __init__(self, *a, **k):
         super().__init__(*a, **k)
         self.struct_size = C.sizeof(VideoParams)
+
+
+class Conv2dF32Args(C.Structure):
+    """dove_conv2d_f32_args (include/dove_hip.h).  ``struct_size`` is filled in on construction, like ConvDesc."""
+    _fields_ = [("struct_size", C.c_uint), ("reserved", C.c_uint),
+                ("x", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("scale", C.c_void_p), ("shift", C.c_void_p), ("out", C.c_void_p),
+                ("n", C.c_int), ("h", C.c_int), ("w_in", C.c_int), ("cin", C.c_int), ("cout", C.c_int), ("kh", C.c_int), ("kw", C.c_int),
+                ("stride", C.c_int), ("act", C.c_int), ("out_mul", C.c_float), ("ldx", C.c_longlong), ("ldo", C.c_longlong)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size = C.sizeof(Conv2dF32Args)
 
 
 class PreNoise(C.Structure):
@@ -188,6 +201,17 @@ SIGNATURES = {
     "dove_video_end_of_input": [_VP],
     "dove_video_need": [_VP, _PLL, _PI],
     "dove_video_step": [_VP, _VP, C.c_size_t, _PI, _PI, _VP],
+    # optical flow (csrc/flow.hip): fp32 channels-last operators with pixel strides, and the warping error
+    "dove_conv2d_f32": [C.POINTER(Conv2dF32Args), _VP],
+    "dove_instance_norm_f32": [_VP, _I, _I, _I, _I, _VP, _I, _F, _VP, C.c_size_t, _VP, _VP],
+    "dove_corr_volume_f32": [_VP, _VP, _I, _I, _I, _I, _F, _VP, _VP],
+    "dove_avgpool2_f32": [_VP, _LL, _I, _I, _VP, _VP],
+    "dove_corr_lookup_f32": [_VP, _VP, _VP, _VP, _VP, _LL, _I, _I, _I, _I, _VP, _VP],
+    "dove_gru_gate_f32": [_VP, _LL, _VP, _LL, _I, _I, _LL, _VP, _VP],
+    "dove_gru_update_f32": [_VP, _LL, _VP, _LL, _VP, _LL, _I, _LL, _VP],
+    "dove_add_f32": [_VP, _LL, _VP, _LL, _VP, _LL, _I, _LL, _I, _VP],
+    "dove_convex_upsample_f32": [_VP, _LL, _VP, _I, _I, _I, _VP, _VP],
+    "dove_flow_warp_error": [_VP, _VP, _I, _VP, _VP, _I, _I, _I, _VP, C.c_size_t, _VP, _VP, _VP, _VP],
 }
 PLAIN = {"dove_last_error": (C.c_char_p, []), "dove_abi_version": (C.c_int, []), "dove_comm_destroy": (None, [C.c_void_p]),
          "dove_conv_gn_partial_rows": (C.c_longlong, [C.POINTER(ConvDesc)]),
@@ -210,7 +234,9 @@ PLAIN = {"dove_last_error": (C.c_char_p, []), "dove_abi_version": (C.c_int, []),
          "dove_chunk_planner_need": (C.c_longlong, [_VP]),
          "dove_chunk_planner_destroy": (None, [_VP]),
          "dove_video_workspace_bytes": (C.c_size_t, [_VP, C.POINTER(VideoParams)]),
-         "dove_video_close": (None, [_VP])}
+         "dove_video_close": (None, [_VP]),
+         "dove_instance_norm_f32_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I]),
+         "dove_flow_warp_error_workspace_bytes": (C.c_size_t, [_I, _I, _I])}
 
 
 def kernel_source_sha256() -> str:

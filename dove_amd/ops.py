@@ -901,3 +901,168 @@ def attention_bias(qkv: torch.Tensor, bias: torch.Tensor, heads: int) -> torch.T
     L.check(L.load().dove_attention_bias_bf16(C.c_void_p(base), C.c_void_p(base + 2 * D), C.c_void_p(base + 4 * D), 3 * D, L.ptr(bias),
                                               L.ptr(out), D, N, heads, 64, L.stream_ptr()), "dove_attention_bias_bf16")
     return out
+
+
+# ---- optical flow (csrc/flow.hip): fp32 channels-last operators that read and fill channel slices ---------------------------------
+def _cl_f32(t: torch.Tensor, what: str) -> int:
+    """Check a float32 [N,H,W,C] tensor or channel-slice view of one (``buf[..., a:b]``) -> its pixel stride in elements."""
+    if t.dtype != torch.float32 or t.dim() != 4 or not t.is_cuda:
+        raise ValueError(f"{what}: need a float32 [N,H,W,C] tensor on the HIP device, got {tuple(t.shape)} {t.dtype} on {t.device}")
+    N, H, W, Cc = t.shape
+    ld = t.stride(2) if W > 1 else (t.stride(1) if H > 1 else (t.stride(0) if N > 1 else Cc))
+    ok = (Cc == 1 or t.stride(3) == 1) and ld >= Cc and (W == 1 or t.stride(2) == ld) and (H == 1 or t.stride(1) == W * ld) and \
+         (N == 1 or t.stride(0) == H * W * ld)
+    if not ok:
+        raise ValueError(f"{what}: {tuple(t.shape)} with strides {t.stride()} is not a channel slice of a contiguous [N,H,W,ld] buffer")
+    return int(ld)
+
+
+def conv2d_f32(x: torch.Tensor, w: torch.Tensor, bias=None, *, stride: int = 1, act: int = 0, scale=None, shift=None, out_mul: float = 1.0,
+               out: torch.Tensor | None = None) -> torch.Tensor:
+    """x [N,H,W,Cin] (a channel slice is fine), w float32 [kh,kw,Cin,Cout] -> out [N,Ho,Wo,Cout] = out_mul * act(scale * (conv + bias) +
+    shift), zero padding k // 2.  ``out`` may be a channel slice of a wider buffer: only that slice is written."""
+    ldx = _cl_f32(x, "conv2d_f32 x")
+    L.require_cuda(w, bias, scale, shift)
+    N, H, W, cin = x.shape
+    if w.dtype != torch.float32 or w.dim() != 4 or w.shape[2] != cin:
+        raise ValueError(f"conv2d_f32: w {tuple(w.shape)} {w.dtype} must be float32 [kh,kw,{cin},Cout]")
+    kh, kw, _, cout = w.shape
+    for nm, v in (("bias", bias), ("scale", scale), ("shift", shift)):
+        if v is not None and (v.dtype != torch.float32 or v.numel() != cout):
+            raise ValueError(f"conv2d_f32: {nm} must be float32 [{cout}]")
+    ho, wo = (H + 2 * (kh // 2) - kh) // stride + 1, (W + 2 * (kw // 2) - kw) // stride + 1
+    if out is None:
+        out = torch.empty(N, ho, wo, cout, dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != (N, ho, wo, cout):
+        raise ValueError(f"conv2d_f32: out {tuple(out.shape)} must be {(N, ho, wo, cout)}")
+    a = L.Conv2dF32Args()
+    a.x, a.w, a.out = x.data_ptr(), w.data_ptr(), out.data_ptr()
+    a.bias = bias.data_ptr() if bias is not None else None
+    a.scale = scale.data_ptr() if scale is not None else None
+    a.shift = shift.data_ptr() if shift is not None else None
+    a.n, a.h, a.w_in, a.cin, a.cout, a.kh, a.kw, a.stride, a.act, a.out_mul = N, H, W, cin, cout, kh, kw, stride, act, out_mul
+    a.ldx, a.ldo = ldx, _cl_f32(out, "conv2d_f32 out")
+    L.check(L.load().dove_conv2d_f32(C.byref(a), L.stream_ptr()), "dove_conv2d_f32")
+    return out
+
+
+def instance_norm_f32(x: torch.Tensor, relu: bool = False, resid: torch.Tensor | None = None, eps: float = 1e-5) -> torch.Tensor:
+    """InstanceNorm2d (no affine, biased variance) of contiguous float32 [N,H,W,C]; ``relu``: max(., 0); ``resid``: max(resid + ., 0)."""
+    L.require_cuda(x, resid)
+    if x.dtype != torch.float32 or x.dim() != 4 or (resid is not None and (resid.shape != x.shape or resid.dtype != x.dtype)):
+        raise ValueError(f"instance_norm_f32: x {tuple(x.shape)} {x.dtype} must be float32 [N,H,W,C] and resid of the same shape")
+    N, H, W, Cc = x.shape
+    lib = L.load()
+    ws = torch.empty(max(int(lib.dove_instance_norm_f32_workspace_bytes(N, H, W, Cc)), 8), dtype=torch.uint8, device=x.device)
+    out = torch.empty_like(x)
+    L.check(lib.dove_instance_norm_f32(L.ptr(x), N, H, W, Cc, L.ptr(resid), int(bool(relu)), eps, L.ptr(ws), ws.numel(), L.ptr(out),
+                                       L.stream_ptr()), "dove_instance_norm_f32")
+    return out
+
+
+def corr_pyramid_f32(fmap1: torch.Tensor, fmap2: torch.Tensor) -> list:
+    """fmaps contiguous float32 [N,H,W,C] -> the all-pairs volume [N*H*W,H,W] scaled by 1/sqrt(C) and its three 2x2 average pools."""
+    L.require_cuda(fmap1, fmap2)
+    if fmap1.dtype != torch.float32 or fmap1.dim() != 4 or fmap2.shape != fmap1.shape or fmap2.dtype != fmap1.dtype:
+        raise ValueError(f"corr_pyramid_f32: fmaps {tuple(fmap1.shape)} / {tuple(fmap2.shape)} must be the same float32 [N,H,W,C]")
+    N, H, W, Cc = fmap1.shape
+    lib = L.load()
+    levels = [torch.empty(N * H * W, H, W, dtype=torch.float32, device=fmap1.device)]
+    L.check(lib.dove_corr_volume_f32(L.ptr(fmap1), L.ptr(fmap2), N, H, W, Cc, 1.0 / math.sqrt(Cc), L.ptr(levels[0]), L.stream_ptr()),
+            "dove_corr_volume_f32")
+    for _ in range(3):
+        src = levels[-1]
+        dst = torch.empty(src.shape[0], src.shape[1] // 2, src.shape[2] // 2, dtype=torch.float32, device=src.device)
+        L.check(lib.dove_avgpool2_f32(L.ptr(src), src.shape[0], src.shape[1], src.shape[2], L.ptr(dst), L.stream_ptr()), "dove_avgpool2_f32")
+        levels.append(dst)
+    return levels
+
+
+def corr_lookup_f32(levels, coords: torch.Tensor, add_grid: bool = False, out: torch.Tensor | None = None) -> torch.Tensor:
+    """levels: corr_pyramid_f32's four; coords [N,H,W,2] (x, y; a channel slice is fine; ``add_grid``: a flow, the pixel grid is added) ->
+    [N,H,W,324]: channel = level * 81 + a * 9 + b samples (x / 2^level + a - 4, y / 2^level + b - 4)."""
+    ldc = _cl_f32(coords, "corr_lookup_f32 coords")
+    N, H, W, two = coords.shape
+    if two != 2 or len(levels) != 4 or any(tuple(l.shape) != (N * H * W, H >> i, W >> i) or not l.is_contiguous() for i, l in enumerate(levels)):
+        raise ValueError(f"corr_lookup_f32: coords {tuple(coords.shape)} and levels {[tuple(l.shape) for l in levels]} do not match")
+    if out is None:
+        out = torch.empty(N, H, W, 324, dtype=torch.float32, device=coords.device)
+    L.check(L.load().dove_corr_lookup_f32(*(L.ptr(l) for l in levels), L.ptr(coords), ldc, int(bool(add_grid)), N, H, W, L.ptr(out),
+                                          L.stream_ptr()), "dove_corr_lookup_f32")
+    return out
+
+
+def gru_gate_f32(r: torch.Tensor, hx: torch.Tensor, ch_h: int, rhx: torch.Tensor) -> torch.Tensor:
+    """rhx[..., :ch_h] = r * hx[..., :ch_h], rhx[..., ch_h:] = hx[..., ch_h:]; hx, rhx contiguous [N,H,W,C], r [N,H,W,ch_h] (slice fine)."""
+    ldr = _cl_f32(r, "gru_gate_f32 r")
+    L.require_cuda(hx, rhx)
+    if hx.shape != rhx.shape or r.shape[:3] != hx.shape[:3] or r.shape[3] != ch_h or hx.dtype != torch.float32 or rhx.dtype != torch.float32:
+        raise ValueError("gru_gate_f32: shapes do not match")
+    npix = hx.shape[0] * hx.shape[1] * hx.shape[2]
+    L.check(L.load().dove_gru_gate_f32(L.ptr(r), ldr, L.ptr(hx), hx.shape[3], ch_h, hx.shape[3], npix, L.ptr(rhx), L.stream_ptr()),
+            "dove_gru_gate_f32")
+    return rhx
+
+
+def gru_update_f32(z: torch.Tensor, q: torch.Tensor, hx: torch.Tensor) -> torch.Tensor:
+    """hx[..., :ch_h] = (1 - z) * hx[..., :ch_h] + z * q in place; z, q [N,H,W,ch_h] (slices fine), hx contiguous [N,H,W,C]."""
+    ldz, ldq = _cl_f32(z, "gru_update_f32 z"), _cl_f32(q, "gru_update_f32 q")
+    L.require_cuda(hx)
+    if z.shape != q.shape or z.shape[:3] != hx.shape[:3] or z.shape[3] > hx.shape[3] or hx.dtype != torch.float32:
+        raise ValueError("gru_update_f32: shapes do not match")
+    npix = hx.shape[0] * hx.shape[1] * hx.shape[2]
+    L.check(L.load().dove_gru_update_f32(L.ptr(z), ldz, L.ptr(q), ldq, L.ptr(hx), hx.shape[3], z.shape[3], npix, L.stream_ptr()),
+            "dove_gru_update_f32")
+    return hx
+
+
+def add_f32(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor | None = None, relu: bool = False) -> torch.Tensor:
+    """out = a + b (``relu``: max(., 0)) on float32 [N,H,W,C] tensors or channel slices; ``out`` may be ``a`` or ``b``."""
+    lda, ldb = _cl_f32(a, "add_f32 a"), _cl_f32(b, "add_f32 b")
+    if out is None:
+        out = torch.empty(a.shape, dtype=torch.float32, device=a.device)
+    if a.shape != b.shape or out.shape != a.shape:
+        raise ValueError("add_f32: shapes do not match")
+    npix = a.shape[0] * a.shape[1] * a.shape[2]
+    L.check(L.load().dove_add_f32(L.ptr(a), lda, L.ptr(b), ldb, L.ptr(out), _cl_f32(out, "add_f32 out"), a.shape[3], npix, int(bool(relu)),
+                                  L.stream_ptr()), "dove_add_f32")
+    return out
+
+
+def convex_upsample_f32(flow: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
+    """flow [N,H,W,2] (a channel slice is fine), mask contiguous [N,H,W,576] -> [N,2,8H,8W]: RAFT's convex combination of the 3x3
+    neighbours of 8 * flow under softmax(mask) over the 9 taps."""
+    ldf = _cl_f32(flow, "convex_upsample_f32 flow")
+    L.require_cuda(mask)
+    N, H, W, two = flow.shape
+    if two != 2 or tuple(mask.shape) != (N, H, W, 576) or mask.dtype != torch.float32:
+        raise ValueError(f"convex_upsample_f32: flow {tuple(flow.shape)} and mask {tuple(mask.shape)} must be [N,H,W,2] and [N,H,W,576]")
+    out = torch.empty(N, 2, 8 * H, 8 * W, dtype=torch.float32, device=flow.device)
+    L.check(L.load().dove_convex_upsample_f32(L.ptr(flow), ldf, L.ptr(mask), N, H, W, L.ptr(out), L.stream_ptr()), "dove_convex_upsample_f32")
+    return out
+
+
+def flow_warp_error(img1: torch.Tensor, img2: torch.Tensor, flow_fw: torch.Tensor, flow_bw: torch.Tensor, want_warped: bool = False,
+                    want_mask: bool = False):
+    """img1, img2 [N,H,W,3] uint8 (read as value / 255) or float32 in [0, 1]; flow_fw, flow_bw float32 [N,2,H,W] ->
+    (sums fp64 [N,2] = {masked squared error, mask count}, warped [N,H,W,3] or None, mask uint8 [N,H,W] or None: bit 0 the
+    forward-backward check, bit 1 "the sample position lies inside the frame")."""
+    L.require_cuda(img1, img2, flow_fw, flow_bw)
+    if img1.dim() != 4 or img1.shape[3] != 3 or img2.shape != img1.shape or img2.dtype != img1.dtype or \
+            img1.dtype not in (torch.uint8, torch.float32):
+        raise ValueError(f"flow_warp_error: images {tuple(img1.shape)} {img1.dtype} / {tuple(img2.shape)} {img2.dtype} must be the same "
+                         "uint8 or float32 [N,H,W,3]")
+    N, H, W, _ = img1.shape
+    for f in (flow_fw, flow_bw):
+        if f.dtype != torch.float32 or tuple(f.shape) != (N, 2, H, W):
+            raise ValueError(f"flow_warp_error: flow {tuple(f.shape)} {f.dtype} must be float32 {(N, 2, H, W)}")
+    lib = L.load()
+    dev = img1.device
+    ws = torch.empty(max(int(lib.dove_flow_warp_error_workspace_bytes(N, H, W)), 8), dtype=torch.uint8, device=dev)
+    sums = torch.empty(N, 2, dtype=torch.float64, device=dev)
+    warped = torch.empty(N, H, W, 3, dtype=torch.float32, device=dev) if want_warped else None
+    mask = torch.empty(N, H, W, dtype=torch.uint8, device=dev) if want_mask else None
+    L.check(lib.dove_flow_warp_error(L.ptr(img1), L.ptr(img2), L.U8 if img1.dtype == torch.uint8 else L.F32, L.ptr(flow_fw), L.ptr(flow_bw),
+                                     N, H, W, L.ptr(ws), ws.numel(), L.ptr(sums), L.ptr(warped), L.ptr(mask), L.stream_ptr()),
+            "dove_flow_warp_error")
+    return sums, warped, mask

@@ -669,6 +669,69 @@ int dove_video_need(const dove_video* v, long long* frames, int* end_of_input);
 int dove_video_step(dove_video* v, void* out, size_t out_bytes, int* frames_written, int* done, void* stream);
 void dove_video_close(dove_video* v);
 
+/* Optical flow (RAFT) and the warping error (csrc/flow.hip).  Everything is fp32 on the f32-input MFMA or the fp32 / fp64
+ * VALU; activations are channels-last [n][h][w][c] fp32 whose pixel stride (ldx, ldo, ld...) may exceed c, so an operator reads or fills a
+ * channel slice of a wider buffer (pass the pointer of the slice's first channel).  Nothing outside a written slice is touched.  No call
+ * uses atomics: two calls give identical bits, and the result for one image does not depend on what else is in the batch.
+ *   conv2d_f32: zero padding k / 2, kh, kw in {1, 3, 5, 7}, stride 1 or 2; w is [kh][kw][cin][cout] fp32 (tap-major K, cout contiguous).
+ *     out = out_mul * act(scale * (conv + bias) + shift); bias, scale / shift (per output channel) may be NULL.  Each output is one fp32 FMA
+ *     chain in K order.  sigmoid and tanh are evaluated in fp64 and rounded once.
+ *   instance_norm_f32: per (n, c) over h x w, biased variance, no affine: y = (x - mean) / sqrt(var + eps); relu != 0: y = max(y, 0);
+ *     resid != NULL: y = max(resid + y, 0).  x, resid, out dense [n][h][w][c]; out may alias x.  Statistics in fp64 (256-pixel partials merged in
+ *     order).  ws: device scratch of dove_instance_norm_f32_workspace_bytes.
+ *   corr_volume_f32: out [n][h w][h w] = scale * sum_c fmap1[n][p][c] fmap2[n][q][c] (p the row), fmaps dense [n][h][w][c].
+ *   avgpool2_f32: x [planes][h][w] -> out [planes][h / 2][w / 2], 2 x 2 means, odd sizes floored.
+ *   corr_lookup_f32: levels l = 0..3 are [n h w][h >> l][w >> l] (the volume and its three pools).  For pixel p with centre (cx, cy) = coords[p ldc],
+ *     coords[p ldc + 1] (add_grid != 0: plus the pixel's own (x, y)), out[p][l 81 + a 9 + b] is the bilinear sample (zeros outside, corners
+ *     aligned) of plane p of level l at (cx / 2^l + a - 4, cy / 2^l + b - 4): the window's first index moves x, as the reference's CorrBlock does.
+ *     out dense [n][h][w][324]; h, w >= 8.
+ *   gru_gate_f32: rhx[p][c] = c < ch_h ? r[p][c] * hx[p][c] : hx[p][c] for c < ch (hx, rhx of pixel stride ld; r of ldr).
+ *   gru_update_f32: hx[p][c] = (1 - z) hx[p][c] + z q for c < ch_h.
+ *   add_f32: out = a + b over ch channels of npix pixels, relu != 0: max(., 0).  out may alias a or b.
+ *   convex_upsample_f32: flow [n][h][w] pixels of stride ldf (x, y first), mask dense [n][h][w][576] with channel = tap 64 + i 8 + j ->
+ *     out [n][2][8 h][8 w]: out[c][8 y + i][8 x + j] = sum_tap softmax_tap(mask) 8 flow[c] at the 3 x 3 neighbour `tap` (zero outside).
+ *   flow_warp_error: n frame pairs.  img1, img2 [n][h][w][3] (DOVE_U8: value / 255; DOVE_F32: as is), flow_fw, flow_bw [n][2][h][w] fp32 (x, y).
+ *     With s = (x, y) + flow_fw: b~ = bilinear(flow_bw, s), warp = bilinear(img2, s) (zeros outside, corners aligned);
+ *     fb = |flow_fw + b~|^2 < 0.01 (|flow_fw|^2 + |b~|^2) + 0.5; inside = s within [0, w - 1] x [0, h - 1].
+ *     out[n][2] fp64 = {sum over pixels with fb and inside of sum_c (img1 - warp)^2, the number of such pixels}.  warped (may be NULL):
+ *     [n][h][w][3] fp32; mask (may be NULL): [n][h][w] u8, bit 0 = fb, bit 1 = inside.  ws: dove_flow_warp_error_workspace_bytes. */
+#define DOVE_ACT_NONE 0
+#define DOVE_ACT_RELU 1
+#define DOVE_ACT_SIGMOID 2
+#define DOVE_ACT_TANH 3
+typedef struct dove_conv2d_f32_args {
+  unsigned int struct_size; /* = sizeof(dove_conv2d_f32_args) of the caller's header, as dove_conv_desc */
+  unsigned int reserved;    /* 0 */
+  const float* x;           /* [n][h][w_in] pixels of stride ldx, cin channels read */
+  const float* w;           /* [kh][kw][cin][cout] */
+  const float* bias;        /* [cout] or NULL */
+  const float* scale;       /* [cout] or NULL; with shift */
+  const float* shift;
+  float* out;               /* [n][ho][wo] pixels of stride ldo, cout channels written; ho = (h + 2 (kh / 2) - kh) / stride + 1 */
+  int n, h, w_in, cin, cout, kh, kw, stride;
+  int act;                  /* DOVE_ACT_* */
+  float out_mul;            /* 1 for none */
+  long long ldx, ldo;
+} dove_conv2d_f32_args;
+int dove_conv2d_f32(const dove_conv2d_f32_args* args, void* stream);
+size_t dove_instance_norm_f32_workspace_bytes(int n, int h, int w, int c);
+int dove_instance_norm_f32(const float* x, int n, int h, int w, int c, const float* resid, int relu, float eps, void* ws, size_t ws_bytes,
+                           float* out, void* stream);
+int dove_corr_volume_f32(const float* fmap1, const float* fmap2, int n, int h, int w, int c, float scale, float* out, void* stream);
+int dove_avgpool2_f32(const float* x, long long planes, int h, int w, float* out, void* stream);
+int dove_corr_lookup_f32(const float* level0, const float* level1, const float* level2, const float* level3, const float* coords,
+                         long long ldc, int add_grid, int n, int h, int w, float* out, void* stream);
+int dove_gru_gate_f32(const float* r, long long ldr, const float* hx, long long ld, int ch_h, int ch, long long npix, float* rhx,
+                      void* stream);
+int dove_gru_update_f32(const float* z, long long ldz, const float* q, long long ldq, float* hx, long long ld, int ch_h, long long npix,
+                        void* stream);
+int dove_add_f32(const float* a, long long lda, const float* b, long long ldb, float* out, long long ldo, int ch, long long npix, int relu,
+                 void* stream);
+int dove_convex_upsample_f32(const float* flow, long long ldf, const float* mask, int n, int h, int w, float* out, void* stream);
+size_t dove_flow_warp_error_workspace_bytes(int n, int h, int w);
+int dove_flow_warp_error(const void* img1, const void* img2, int dtype, const float* flow_fw, const float* flow_bw, int n, int h, int w,
+                         void* ws, size_t ws_bytes, double* out, float* warped, unsigned char* mask, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
