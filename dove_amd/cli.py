@@ -9,7 +9,7 @@ frame rate and chroma layout of the ``<clip>.y4m`` written: YUV4MPEG2, dove_amd.
 calls ``pipe.enable_sequential_cpu_offload()`` like the reference (a no-op with 288 GB of HBM); ``--eval_metrics`` knows ``psnr`` and
 ``ssim``, computed on the GPU (dove_amd.metrics) from the uint8 frames written to disk against ``--gt_dir/<clip>``, as the reference's
 ``eval_metrics.py`` scores the saved files; the per-clip values go to ``metrics_<names>.json`` in ``--output_path`` (the reference's
-structure, ref :755-776); the network metrics of pyiqa (lpips, dists, clipiqa, ...) are not provided; ``--dtype`` other than bfloat16 is refused.  Inputs are PNG folders,
+structure, ref :755-776); ``--metric_weights DIR`` adds ``lpips``, ``lpips-vgg`` and ``dists`` from checkpoints in that directory (dove_amd.percep); without it they, and always the other network metrics of pyiqa (clipiqa, ...), are refused; ``--dtype`` other than bfloat16 is refused.  Inputs are PNG folders,
 ``.npy`` clips (uint8 [F,H,W,3]) or ``.y4m`` files because H.264 decoding (decord) is outside the accelerated path; outputs are PNG
 folders, ``.npy`` or ``.y4m`` (``--y4m_save``; streamed chunk by chunk when ``--chunk_len > 0``).  ``--random_init`` builds the CogVideoX1.5-5B architecture with synthetic weights (no checkpoint is
 available offline).  ``--eval_psnr_dir`` computes plain PSNR (10*log10(1/MSE), per-frame mean) on the CPU against ground-truth folders; with it,
@@ -140,7 +140,10 @@ def main(argv=None):
     ap.add_argument("--input_json", type=str, default=None, help="{clip name: prompt}; clips without an entry use the empty prompt (ref :590-594, :676)")
     ap.add_argument("--output_path", type=str, default="./results")
     ap.add_argument("--gt_dir", type=str, default=None, help="ground-truth folders / .npy / .y4m clips for --eval_metrics (ref :511)")
-    ap.add_argument("--eval_metrics", type=str, default="", help="any of 'psnr,ssim' (ref :513), on the GPU; the network metrics of pyiqa (lpips, ...) are not provided")
+    ap.add_argument("--eval_metrics", type=str, default="", help="any of 'psnr,ssim' (ref :513), on the GPU; with --metric_weights also 'lpips,lpips-vgg,dists'; the other network metrics of pyiqa are not provided")
+    ap.add_argument("--metric_weights", type=str, default="",
+                    help="directory with the checkpoints of lpips / lpips-vgg / dists for --eval_metrics (alexnet*.pth, vgg16*.pth, "
+                         "LPIPS_v0.1_alex*.pth, LPIPS_v0.1_vgg*.pth, DISTS_weights*.pth; dove_amd.percep)")
     ap.add_argument("--png_save", action="store_true")
     ap.add_argument("--y4m_save", action="store_true",
                     help="write <clip>.y4m (YUV4MPEG2) with --fps and --save_format; with --chunk_len > 0 it is streamed chunk by chunk")
@@ -149,14 +152,22 @@ def main(argv=None):
     args = ap.parse_args(argv)
     check_dtype(args)
     metrics = [m.strip().lower() for m in args.eval_metrics.split(",") if m.strip()]
-    if any(m not in ("psnr", "ssim") for m in metrics):
-        raise NotImplementedError(f"--eval_metrics {args.eval_metrics}: only 'psnr' and 'ssim' are computed here; the other pyiqa metrics "
-                                  "need network weights and are outside the path")
+    network = ("lpips", "lpips-vgg", "dists") if args.metric_weights else ()
+    if any(m not in ("psnr", "ssim") + network for m in metrics):
+        known = "'psnr', 'ssim', 'lpips', 'lpips-vgg' and 'dists'" if network else "'psnr' and 'ssim'"
+        raise NotImplementedError(f"--eval_metrics {args.eval_metrics}: only {known} are computed here; " +
+                                  ("the other pyiqa metrics are outside the path" if network else
+                                   "the other pyiqa metrics need network weights and are outside the path "
+                                   "(--metric_weights DIR adds lpips, lpips-vgg and dists)"))
     if metrics and not (args.gt_dir or args.eval_psnr_dir):
         raise ValueError(f"--eval_metrics {args.eval_metrics} needs --gt_dir")
     # with --eval_psnr_dir, PSNR stays on that flag's CPU path (against its folders, as before); the rest runs on the GPU against
     # --gt_dir (or the --eval_psnr_dir folders when --gt_dir is not given)
     gpu_metrics = [m for m in metrics if not (m == "psnr" and args.eval_psnr_dir)]
+    metric_weights = {}
+    if args.metric_weights:
+        from .percep import load_metric_weights
+        metric_weights = {m: load_metric_weights(args.metric_weights, m) for m in metrics if m in network}
     metrics_gt = args.gt_dir or args.eval_psnr_dir
     y4m_chroma = None
     if args.y4m_save:
@@ -239,7 +250,7 @@ def main(argv=None):
         if gpu_metrics:
             from .metrics import clip_metrics
             gt = prepost.load_frames(os.path.join(metrics_gt, name), **yuv_in)
-            vals = clip_metrics(frames_out, gt, gpu_metrics)
+            vals = clip_metrics(frames_out, gt, gpu_metrics, weights=metric_weights)
             for m in gpu_metrics:
                 print(f"[{name}] {m.upper()}={vals[m]:.4f}")
         for m in metrics:

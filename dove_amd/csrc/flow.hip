@@ -456,6 +456,30 @@ extern "C" int dove_conv2d_f32(const dove_conv2d_f32_args* a, void* stream) {
   return DOVE_OK;
 }
 
+// The general walk of dove_convnet_conv_f32 (percep.hip checks the arguments): conv_f32_kernel with the caller's padding and stride.
+__attribute__((visibility("hidden"))) int dove_conv_f32_general_launch(const float* x, const float* w, const float* bias, float* out, int n,
+                                                                       int h, int w_in, int cin, int cout, int kh, int kw, int stride,
+                                                                       int pad_h, int pad_w, int relu, long long ldx, long long ldo,
+                                                                       void* stream) {
+  ConvP p;
+  p.x = x; p.w = w; p.bias = bias; p.scale = p.shift = nullptr; p.out = out;
+  p.H = h; p.W = w_in; p.Cin = cin; p.Cout = cout; p.kw = kw; p.stride = stride; p.act = relu ? DOVE_ACT_RELU : DOVE_ACT_NONE;
+  p.ph = pad_h; p.pw = pad_w;
+  p.Ho = (h + 2 * pad_h - kh) / stride + 1;
+  p.Wo = (w_in + 2 * pad_w - kw) / stride + 1;
+  p.M = (long long)n * p.Ho * p.Wo;
+  const long long K = (long long)kh * kw * cin;
+  DOVE_CHECK_ARG(p.M <= 0x7fffffffLL * BM / 2 && (long long)n * h * w_in < (1LL << 40) && K < (1 << 24),
+                 "dove_convnet_conv_f32: problem too large");
+  p.K = (int)K;
+  p.ldx = ldx; p.ldo = ldo; p.ldwk = cout; p.ldwn = 1; p.bx = p.bw = p.bo = 0;
+  p.mul = 1.f;
+  dim3 grid((unsigned)((p.M + BM - 1) / BM), (unsigned)((cout + BN - 1) / BN), 1);
+  hipLaunchKernelGGL(conv_f32_kernel<false>, grid, dim3(NT), 0, (hipStream_t)stream, p);
+  DOVE_CHECK_LAUNCH("dove_convnet_conv_f32");
+  return DOVE_OK;
+}
+
 static size_t inorm_ws(int n, int h, int w, int c) {
   const long long S = ((long long)h * w + IN_SLICE - 1) / IN_SLICE;
   return (size_t)((long long)n * c * S * 2 * sizeof(double) + (long long)n * c * 2 * sizeof(float));

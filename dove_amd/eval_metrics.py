@@ -6,8 +6,10 @@ ground truth by ``os.path.splitext`` stem, the same per-clip steps (match_resolu
 same JSON (``metrics_<names>.json``: per_sample {clip: {metric: round(value, 4)}}, average of the rounded values, count).
 Inputs are PNG/JPG folders, single images, ``.npy`` clips (uint8 [F,H,W,3]) and ``.y4m`` files (YUV4MPEG2, read as bt601 with the
 stream's range tag; dove_amd.y4m); mp4 decoding is not provided.  ``--metrics``
-defaults to ``psnr,ssim`` (the reference's default also lists clipiqa, which needs network weights); a metric other than psnr / ssim
-fails to initialise with a message, as a pyiqa metric that cannot be created does in the reference."""
+defaults to ``psnr,ssim`` (the reference's default also lists clipiqa, which needs network weights).  ``--metric_weights DIR`` adds
+``lpips``, ``lpips-vgg`` and ``dists`` from the checkpoints in that directory (dove_amd.percep); a file that is absent
+raises FileNotFoundError.  Without the flag a metric other than psnr / ssim fails to initialise with a message, as a pyiqa metric that
+cannot be created does in the reference."""
 from __future__ import annotations
 
 import argparse
@@ -56,22 +58,33 @@ def summarize(results: dict, metrics) -> dict:
     return {"per_sample": results, "average": overall, "count": count}
 
 
-def init_models(metrics, device=None):
+def init_models(metrics, device=None, weights=None):
     models = {}
     for name in metrics:
         try:
-            models[name] = M.create_metric(name).to(device).eval()
+            models[name] = M.create_metric(name, **({"weights": weights[name]} if weights and name in weights else {})).to(device).eval()
         except Exception as e:
             print(f"Failed to initialize metric '{name}': {e}")
     return models
 
 
-def process(gt_root, pred_root, out_path, metrics, batch_mode=False, crop=0, test_y_channel=False, is_center=False) -> dict:
+def load_weights(metrics, directory):
+    """Weights of the network metrics among ``metrics`` from ``--metric_weights`` -> {metric: weights}; without a directory, none (the
+    metrics then fail to initialise, as before).  A file that is absent raises FileNotFoundError."""
+    if not directory:
+        return {}
+    from . import percep
+    return {m: percep.load_metric_weights(directory, m) for m in metrics if m in M.NETWORK_METRICS}
+
+
+def process(gt_root, pred_root, out_path, metrics, batch_mode=False, crop=0, test_y_channel=False, is_center=False,
+            metric_weights=None) -> dict:
     if not torch.cuda.is_available():
         raise RuntimeError("dove_amd.eval_metrics computes PSNR / SSIM on the GPU; no HIP device is visible")
     device = torch.device("cuda")
     print(f"Using device: {device}")
-    models = init_models(metrics, device)
+    weights = load_weights(metrics, metric_weights)
+    models = init_models(metrics, device, weights)
     gt_files, pred_files = pair_files(gt_root, pred_root)
     results = {}
     for name in sorted(pred_files):
@@ -84,9 +97,10 @@ def process(gt_root, pred_root, out_path, metrics, batch_mode=False, crop=0, tes
                 continue
             pred = load_sequence(pred_files[name])
             gt = load_sequence(gt_files[name])
-            fr = [m for m in models if m in FR_METRICS]
+            fr = [m for m in models if m in FR_METRICS or m in weights]
             # batch_mode and per-frame mode both average the per-frame values of the clip; one launch covers all frames either way
-            vals = M.clip_metrics(pred, gt, fr, crop=crop, test_y_channel=test_y_channel, is_center=is_center, name=name) if fr else {}
+            vals = M.clip_metrics(pred, gt, fr, crop=crop, test_y_channel=test_y_channel, is_center=is_center, name=name,
+                                  weights=weights) if fr else {}
             results[name] = {k: round(vals[k], 4) for k in models}
         except Exception as e:
             print(f"Error processing {name}: {e}")
@@ -120,10 +134,13 @@ def main(argv=None):
     parser.add_argument("--crop", type=int, default=0, help="Crop border size for PSNR/SSIM")
     parser.add_argument("--test_y_channel", action="store_true", help="Use Y channel for PSNR/SSIM")
     parser.add_argument("--is_center", action="store_true", help="Use center crop for PSNR/SSIM")
+    parser.add_argument("--metric_weights", type=str, default="",
+                        help="directory with the checkpoints of lpips / lpips-vgg / dists (alexnet*.pth, vgg16*.pth, LPIPS_v0.1_alex*.pth, "
+                             "LPIPS_v0.1_vgg*.pth, DISTS_weights*.pth); without it these metrics are not computed")
     args = parser.parse_args(argv)
     out = args.out or args.pred
     metric_list = [m.strip().lower() for m in args.metrics.split(",")]
-    return process(args.gt, args.pred, out, metric_list, args.batch_mode, args.crop, args.test_y_channel, args.is_center)
+    return process(args.gt, args.pred, out, metric_list, args.batch_mode, args.crop, args.test_y_channel, args.is_center, args.metric_weights)
 
 
 if __name__ == "__main__":

@@ -102,6 +102,19 @@ class Conv2dF32Args(C.Structure):
         self.struct_size = C.sizeof(Conv2dF32Args)
 
 
+class ConvnetConvF32Args(C.Structure):
+    """dove_convnet_conv_f32_args (include/dove_hip.h).  ``struct_size`` is filled in on construction, like ConvDesc."""
+    _fields_ = [("struct_size", C.c_uint), ("reserved", C.c_uint),
+                ("x", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("out", C.c_void_p),
+                ("n", C.c_int), ("h", C.c_int), ("w_in", C.c_int), ("cin", C.c_int), ("cout", C.c_int), ("kh", C.c_int), ("kw", C.c_int),
+                ("stride", C.c_int), ("pad_h", C.c_int), ("pad_w", C.c_int), ("relu", C.c_int), ("reserved2", C.c_int),
+                ("ldx", C.c_longlong), ("ldo", C.c_longlong)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size = C.sizeof(ConvnetConvF32Args)
+
+
 class PreNoise(C.Structure):
     """dove_pre_noise: `--noise_step` of the graph-level dove_sr_clip."""
     _fields_ = [("eps", C.c_void_p), ("eps_dtype", C.c_int), ("sqrt_alpha", C.c_float), ("sqrt_one_minus_alpha", C.c_float)]
@@ -212,6 +225,13 @@ SIGNATURES = {
     "dove_add_f32": [_VP, _LL, _VP, _LL, _VP, _LL, _I, _LL, _I, _VP],
     "dove_convex_upsample_f32": [_VP, _LL, _VP, _I, _I, _I, _VP, _VP],
     "dove_flow_warp_error": [_VP, _VP, _I, _VP, _VP, _I, _I, _I, _VP, C.c_size_t, _VP, _VP, _VP, _VP],
+    # perceptual metrics (csrc/percep.hip): the fp32 trunk operators and the fp64 heads of LPIPS and DISTS; mean / std are host arrays
+    "dove_convnet_conv_f32": [C.POINTER(ConvnetConvF32Args), _VP],
+    "dove_percep_prep_f32": [C.POINTER(ImageView), _I, _I, _I, _I, _F, _F, C.POINTER(C.c_float), C.POINTER(C.c_float), _VP, _VP],
+    "dove_maxpool_f32": [_VP, _LL, _I, _I, _I, _I, _I, _I, _VP, _LL, _VP],
+    "dove_l2pool_f32": [_VP, _LL, _I, _I, _I, _I, _VP, _LL, _VP],
+    "dove_lpips_layer": [_VP, _VP, _LL, _VP, _I, _I, _I, _I, _VP, C.c_size_t, _VP, _VP],
+    "dove_dists_layer": [_VP, _VP, _LL, _VP, _VP, _I, _I, _I, _I, _VP, C.c_size_t, _VP, _VP],
 }
 PLAIN = {"dove_last_error": (C.c_char_p, []), "dove_abi_version": (C.c_int, []), "dove_comm_destroy": (None, [C.c_void_p]),
          "dove_conv_gn_partial_rows": (C.c_longlong, [C.POINTER(ConvDesc)]),
@@ -236,7 +256,10 @@ PLAIN = {"dove_last_error": (C.c_char_p, []), "dove_abi_version": (C.c_int, []),
          "dove_video_workspace_bytes": (C.c_size_t, [_VP, C.POINTER(VideoParams)]),
          "dove_video_close": (None, [_VP]),
          "dove_instance_norm_f32_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I]),
-         "dove_flow_warp_error_workspace_bytes": (C.c_size_t, [_I, _I, _I])}
+         "dove_flow_warp_error_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
+         "dove_convnet_conv_f32_kernel_name": (C.c_char_p, [C.POINTER(ConvnetConvF32Args)]),
+         "dove_lpips_layer_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
+         "dove_dists_layer_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I])}
 
 
 def kernel_source_sha256() -> str:

@@ -3,7 +3,8 @@
 Three surfaces:
   - ``fr_metrics(pred, ref, psnr=True, ssim=True, rgb_to_y=False)``: per-image fp64 values of a batch of strided views;
   - ``create_metric(name)``: pyiqa's ``create_metric`` surface for 'psnr' and 'ssim', so the reference's metric code runs with
-    ``import dove_amd.metrics as pyiqa``; any other name raises ``NotImplementedError`` (the network metrics are not provided);
+    ``import dove_amd.metrics as pyiqa``; ``create_metric(name, weights=W)`` gives 'lpips', 'lpips-vgg' and 'dists' from user-supplied
+    checkpoints (dove_amd.percep); any other name, or one of these without weights, raises ``NotImplementedError``;
   - ``clip_metrics(pred_u8, gt_u8, names, crop, test_y_channel, is_center)``: the per-clip logic of eval_metrics.py (match_resolution,
     crop_border, rgb_to_y, mean over frames), as views on the device.
 
@@ -20,6 +21,7 @@ from . import lib as L
 from . import ops
 
 FR_METRICS = ("psnr", "ssim")
+NETWORK_METRICS = ("lpips", "lpips-vgg", "dists")       # computed by dove_amd.percep when the caller passes weights
 
 
 def _unsupported(name: str) -> NotImplementedError:
@@ -83,9 +85,17 @@ class FRMetric(torch.nn.Module):
         return psnr if self.metric_name == "psnr" else ssim
 
 
-def create_metric(name: str, **kwargs) -> FRMetric:
-    """``pyiqa.create_metric`` for the full-reference metrics computed here ('psnr', 'ssim' with pyiqa's default options)."""
+def create_metric(name: str, weights=None, **kwargs):
+    """``pyiqa.create_metric`` for the full-reference metrics computed here: 'psnr' and 'ssim' with pyiqa's default options, and, given
+    ``weights`` (percep.LpipsWeights / percep.DistsWeights), 'lpips', 'lpips-vgg' and 'dists' (lower is better, [N] fp64)."""
     key = name.strip().lower()
+    if weights is not None:
+        if key not in NETWORK_METRICS:
+            raise NotImplementedError(f"create_metric('{name}', weights=...): weights belong to {', '.join(NETWORK_METRICS)}")
+        if kwargs:
+            raise NotImplementedError(f"create_metric('{name}', {sorted(kwargs)}): only pyiqa's default options are implemented")
+        from . import percep
+        return percep.PerceptualMetric(key, weights)
     if key not in FR_METRICS:
         raise _unsupported(name)
     if kwargs:
@@ -124,20 +134,36 @@ def crop_border(t: torch.Tensor, crop: int) -> torch.Tensor:
     return t[:, crop:-crop, crop:-crop] if crop > 0 else t
 
 
+def rgb_to_y(frames: torch.Tensor) -> torch.Tensor:
+    """eval_metrics.py rgb_to_y on [F,H,W,3] frames (uint8 is read as u / 255) -> float32 [F,1,H,W]: 0.257 r + 0.504 g + 0.098 b + 0.0625."""
+    v = frames.float() / 255.0 if frames.dtype == torch.uint8 else frames.float()
+    return (0.257 * v[..., 0] + 0.504 * v[..., 1] + 0.098 * v[..., 2] + 0.0625)[:, None]
+
+
 def clip_metrics(pred_u8: torch.Tensor, gt_u8: torch.Tensor, names, crop: int = 0, test_y_channel: bool = False,
-                 is_center: bool = False, name: str | None = None) -> dict:
+                 is_center: bool = False, name: str | None = None, weights: dict | None = None) -> dict:
     """Per-clip full-reference metrics as eval_metrics.py computes them -> {metric: mean over frames of the per-frame value}.
 
     ``pred_u8`` / ``gt_u8``: [F,H,W,3] uint8 frames (a host tensor is uploaded as uint8).  Steps of the reference: match_resolution
     (common frame count, top-left or centre crop to the common H x W), crop_border, optional rgb_to_y; all of them are views."""
     names = [n.strip().lower() for n in (names.split(",") if isinstance(names, str) else names)]
+    weights = weights or {}
     for n in names:
-        if n not in FR_METRICS:
+        if n not in FR_METRICS and n not in weights:
             raise _unsupported(n)
     dev = pred_u8.device if pred_u8.is_cuda else (gt_u8.device if gt_u8.is_cuda else torch.device("cuda"))
     pred_u8, gt_u8 = pred_u8.to(dev), gt_u8.to(dev)
     gt, pred = match_resolution(gt_u8, pred_u8, is_center=is_center, name=name)
     gt, pred = crop_border(gt, crop), crop_border(pred, crop)
-    psnr, ssim = fr_metrics(pred, gt, psnr="psnr" in names, ssim="ssim" in names, rgb_to_y=test_y_channel, layout="nhwc")
-    vals = {"psnr": psnr, "ssim": ssim}
+    vals = {}
+    if "psnr" in names or "ssim" in names:
+        vals["psnr"], vals["ssim"] = fr_metrics(pred, gt, psnr="psnr" in names, ssim="ssim" in names, rgb_to_y=test_y_channel,
+                                                layout="nhwc")
+    net = [n for n in names if n not in FR_METRICS]
+    if net:
+        # the reference hands the networks the same cropped (and, with --test_y_channel, one-channel) images as PSNR / SSIM;
+        # ``weights`` of a user-supplied checkpoint make the metric, so ``names`` without them were refused above
+        p, g = (rgb_to_y(pred), rgb_to_y(gt)) if test_y_channel else (pred.permute(0, 3, 1, 2), gt.permute(0, 3, 1, 2))
+        for n in net:
+            vals[n] = create_metric(n, weights=weights[n])(p, g)
     return {n: float(vals[n].mean()) for n in names}

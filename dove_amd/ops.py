@@ -1066,3 +1066,123 @@ def flow_warp_error(img1: torch.Tensor, img2: torch.Tensor, flow_fw: torch.Tenso
                                      N, H, W, L.ptr(ws), ws.numel(), L.ptr(sums), L.ptr(warped), L.ptr(mask), L.stream_ptr()),
             "dove_flow_warp_error")
     return sums, warped, mask
+
+
+# ---- perceptual metrics (csrc/percep.hip): the fp32 trunk operators and the fp64 heads of LPIPS and DISTS ---------------------------
+def _convnet_args(x_shape, ldx: int, w_shape, stride: int, pad, relu: bool, ldo: int | None = None) -> "L.ConvnetConvF32Args":
+    N, H, W, cin = x_shape
+    kh, kw, _, cout = w_shape
+    a = L.ConvnetConvF32Args()
+    a.n, a.h, a.w_in, a.cin, a.cout, a.kh, a.kw, a.stride, a.pad_h, a.pad_w, a.relu = N, H, W, cin, cout, kh, kw, stride, pad[0], pad[1], int(relu)
+    a.ldx, a.ldo = ldx, cout if ldo is None else ldo
+    return a
+
+
+def convnet_conv_kernel_name(x_shape, w_shape, stride: int = 1, pad=(1, 1), ldx: int | None = None) -> str:
+    """The kernel ``convnet_conv_f32`` runs for dense, aligned tensors of these shapes ('' for a shape it refuses); needs no device."""
+    a = _convnet_args(x_shape, x_shape[3] if ldx is None else ldx, w_shape, stride, pad, True)
+    a.x = a.w = a.out = 256                                            # placeholders: only their alignment is looked at
+    return L.load().dove_convnet_conv_f32_kernel_name(C.byref(a)).decode()
+
+
+def convnet_conv_f32(x: torch.Tensor, w: torch.Tensor, bias=None, *, stride: int = 1, pad=(1, 1), relu: bool = True,
+                     out: torch.Tensor | None = None, want_name: bool = False):
+    """x [N,H,W,Cin] (a channel slice is fine), w float32 [kh,kw,Cin,Cout] -> out [N,Ho,Wo,Cout] = conv + bias, ReLU'd if ``relu``;
+    kernels up to 11 x 11, stride 1..4, zero padding ``pad`` below the kernel.  ``out`` may be a channel slice of a wider buffer.
+    ``want_name``: also return the kernel that ran."""
+    ldx = _cl_f32(x, "convnet_conv_f32 x")
+    L.require_cuda(w, bias)
+    N, H, W, cin = x.shape
+    if w.dtype != torch.float32 or w.dim() != 4 or w.shape[2] != cin:
+        raise ValueError(f"convnet_conv_f32: w {tuple(w.shape)} {w.dtype} must be float32 [kh,kw,{cin},Cout]")
+    kh, kw, _, cout = w.shape
+    if bias is not None and (bias.dtype != torch.float32 or bias.numel() != cout):
+        raise ValueError(f"convnet_conv_f32: bias must be float32 [{cout}]")
+    ho, wo = (H + 2 * pad[0] - kh) // stride + 1, (W + 2 * pad[1] - kw) // stride + 1
+    if ho < 1 or wo < 1:
+        raise ValueError(f"convnet_conv_f32: image {H} x {W} is smaller than the kernel {kh} x {kw} with padding {tuple(pad)}")
+    if out is None:
+        out = torch.empty(N, ho, wo, cout, dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != (N, ho, wo, cout):
+        raise ValueError(f"convnet_conv_f32: out {tuple(out.shape)} must be {(N, ho, wo, cout)}")
+    a = _convnet_args(x.shape, ldx, w.shape, stride, pad, relu, _cl_f32(out, "convnet_conv_f32 out"))
+    a.x, a.w, a.out = x.data_ptr(), w.data_ptr(), out.data_ptr()
+    a.bias = bias.data_ptr() if bias is not None else None
+    lib = L.load()
+    L.check(lib.dove_convnet_conv_f32(C.byref(a), L.stream_ptr()), "dove_convnet_conv_f32")
+    return (out, lib.dove_convnet_conv_f32_kernel_name(C.byref(a)).decode()) if want_name else out
+
+
+def percep_prep_f32(img: torch.Tensor, pre_mul: float, pre_add: float, mean, std, out: torch.Tensor | None = None) -> torch.Tensor:
+    """img: an [N,C,H,W] view (any strides, no copy), C in {1, 3}, uint8 (read as u / 255) or float32 -> dense float32 [N,H,W,3] =
+    ((pre_mul * v + pre_add) - mean[ch]) / std[ch]; one channel feeds all three."""
+    if img.dim() != 4 or img.shape[1] not in (1, 3) or img.dtype not in (torch.uint8, torch.float32) or not img.is_cuda:
+        raise ValueError(f"percep_prep_f32: need a uint8 / float32 [N,1|3,H,W] view on the HIP device, got {tuple(img.shape)} {img.dtype} "
+                         f"on {img.device}")
+    N, Cc, H, W = img.shape
+    if out is None:
+        out = torch.empty(N, H, W, 3, dtype=torch.float32, device=img.device)
+    elif tuple(out.shape) != (N, H, W, 3) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError(f"percep_prep_f32: out must be contiguous float32 {(N, H, W, 3)}")
+    v = _image_view(img)
+    m3, s3 = (C.c_float * 3)(*[float(t) for t in mean]), (C.c_float * 3)(*[float(t) for t in std])
+    L.check(L.load().dove_percep_prep_f32(C.byref(v), N, Cc, H, W, float(pre_mul), float(pre_add), m3, s3, L.ptr(out), L.stream_ptr()),
+            "dove_percep_prep_f32")
+    return out
+
+
+def maxpool_f32(x: torch.Tensor, k: int, stride: int) -> torch.Tensor:
+    """k x k max pool of stride ``stride`` without padding (floor sizes) of float32 [N,H,W,C] (a channel slice is fine)."""
+    ldx = _cl_f32(x, "maxpool_f32 x")
+    N, H, W, Cc = x.shape
+    if H < k or W < k:
+        raise ValueError(f"maxpool_f32: image {H} x {W} is smaller than the window {k}")
+    out = torch.empty(N, (H - k) // stride + 1, (W - k) // stride + 1, Cc, dtype=torch.float32, device=x.device)
+    L.check(L.load().dove_maxpool_f32(L.ptr(x), ldx, N, H, W, Cc, k, stride, L.ptr(out), Cc, L.stream_ptr()), "dove_maxpool_f32")
+    return out
+
+
+def l2pool_f32(x: torch.Tensor) -> torch.Tensor:
+    """DISTS' L2 pooling of float32 [N,H,W,C]: sqrt(sum_taps g x^2 + 1e-12), g = outer((1/4, 1/2, 1/4)), stride 2, zero padding 1."""
+    ldx = _cl_f32(x, "l2pool_f32 x")
+    N, H, W, Cc = x.shape
+    out = torch.empty(N, (H - 1) // 2 + 1, (W - 1) // 2 + 1, Cc, dtype=torch.float32, device=x.device)
+    L.check(L.load().dove_l2pool_f32(L.ptr(x), ldx, N, H, W, Cc, L.ptr(out), Cc, L.stream_ptr()), "dove_l2pool_f32")
+    return out
+
+
+def _head_pair(x: torch.Tensor, y: torch.Tensor, what: str) -> int:
+    ld = _cl_f32(x, f"{what} x")
+    if y.shape != x.shape or _cl_f32(y, f"{what} y") != ld:
+        raise ValueError(f"{what}: x {tuple(x.shape)} and y {tuple(y.shape)} must have one shape and one pixel stride")
+    return ld
+
+
+def lpips_layer(x: torch.Tensor, y: torch.Tensor, lin: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """x, y float32 [N,H,W,C] feature maps, lin float32 [C]: out[n] (float64 [N]) += mean over pixels of
+    sum_c lin[c] (x / (|x| + 1e-10) - y / (|y| + 1e-10))^2, evaluated in fp64."""
+    ld = _head_pair(x, y, "lpips_layer")
+    N, H, W, Cc = x.shape
+    L.require_cuda(lin, out)
+    if lin.dtype != torch.float32 or lin.numel() != Cc or out.dtype != torch.float64 or tuple(out.shape) != (N,):
+        raise ValueError(f"lpips_layer: lin must be float32 [{Cc}] and out float64 [{N}]")
+    lib = L.load()
+    ws = torch.empty(max(int(lib.dove_lpips_layer_workspace_bytes(N, H, W)), 8), dtype=torch.uint8, device=x.device)
+    L.check(lib.dove_lpips_layer(L.ptr(x), L.ptr(y), ld, L.ptr(lin), N, H, W, Cc, L.ptr(ws), ws.numel(), L.ptr(out), L.stream_ptr()),
+            "dove_lpips_layer")
+    return out
+
+
+def dists_layer(x: torch.Tensor, y: torch.Tensor, alpha: torch.Tensor, beta: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """x, y float32 [N,H,W,C], alpha, beta float64 [C] (already normalised): out[n] (float64 [N]) += sum_c alpha[c] S1 + beta[c] S2 with
+    S1 = (2 mx my + 1e-6) / (mx^2 + my^2 + 1e-6), S2 = (2 cov + 1e-6) / (vx + vy + 1e-6) from fp64 statistics per channel."""
+    ld = _head_pair(x, y, "dists_layer")
+    N, H, W, Cc = x.shape
+    L.require_cuda(alpha, beta, out)
+    if any(t.dtype != torch.float64 or t.numel() != Cc for t in (alpha, beta)) or out.dtype != torch.float64 or tuple(out.shape) != (N,):
+        raise ValueError(f"dists_layer: alpha, beta must be float64 [{Cc}] and out float64 [{N}]")
+    lib = L.load()
+    ws = torch.empty(max(int(lib.dove_dists_layer_workspace_bytes(N, H, W, Cc)), 8), dtype=torch.uint8, device=x.device)
+    L.check(lib.dove_dists_layer(L.ptr(x), L.ptr(y), ld, L.ptr(alpha), L.ptr(beta), N, H, W, Cc, L.ptr(ws), ws.numel(), L.ptr(out),
+                                 L.stream_ptr()), "dove_dists_layer")
+    return out

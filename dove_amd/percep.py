@@ -1,0 +1,318 @@
+"""The perceptual full-reference metrics LPIPS (v0.1, AlexNet or VGG16) and DISTS on the GPU, trunks in exact fp32 (csrc/percep.hip).
+
+The definitions are pyiqa's defaults (``pyiqa.create_metric('lpips' | 'lpips-vgg' | 'dists')``), restated from the published LPIPS v0.1
+and DISTS code:
+
+  LPIPS: images in [0,1] are mapped to 2 v - 1, then (. - shift) / scale per channel; the trunk's five ReLU outputs are tapped (AlexNet:
+    64, 192, 384, 256, 256 channels, 3/2 max-pools before conv2 and conv3; VGG16: relu1_2, 2_2, 3_3, 4_3, 5_3 with 2/2 max-pools between
+    the stages).  Per tap, each pixel's feature vector is divided by (its L2 norm + 1e-10), the squared difference of the two images is
+    weighted by the non-negative ``lin`` vector and averaged over the pixels; the value is the sum over the five taps.
+  DISTS: (v - mean) / std, the same VGG16 convs with an L2 pool (Hann window (1/4, 1/2, 1/4), stride 2) in place of each max-pool.  Six
+    feature sets - the un-normalised image and the five stage outputs, 3 + 64 + 128 + 256 + 512 + 512 = 1475 channels - give per channel
+    S1 = (2 mx my + c) / (mx^2 + my^2 + c) and S2 = (2 cov + c) / (vx + vy + c), c = 1e-6, and the score is
+    1 - sum(alpha S1 + beta S2) / (sum(alpha) + sum(beta)).
+
+The user supplies the checkpoints (torchvision's backbone plus the metric's own small file), as for RAFT.  This module walks the trunk in
+Python; every operator is a kernel of the library.  Prediction and ground truth go through the trunk as one batch, in groups of frames
+sized so that the live activations of a group stay under ``ACTIVATION_BUDGET``; a frame's value does not depend on the grouping.
+"""
+from __future__ import annotations
+
+import glob
+import math
+import os
+import zlib
+from dataclasses import dataclass, field
+
+import numpy as np
+import torch
+
+from . import ops
+from .flow import pack_conv_weight
+from .metrics import _as_nchw
+
+ALEX_CONVS = ((0, 64, 3, 11, 4, 2), (3, 192, 64, 5, 1, 2), (6, 384, 192, 3, 1, 1), (8, 256, 384, 3, 1, 1), (10, 256, 256, 3, 1, 1))
+VGG_STAGES = (((0, 64, 3), (2, 64, 64)), ((5, 128, 64), (7, 128, 128)), ((10, 256, 128), (12, 256, 256), (14, 256, 256)),
+              ((17, 512, 256), (19, 512, 512), (21, 512, 512)), ((24, 512, 512), (26, 512, 512), (28, 512, 512)))
+LPIPS_CHANNELS = {"alex": (64, 192, 384, 256, 256), "vgg": (64, 128, 256, 512, 512)}
+DISTS_CHANNELS = (3, 64, 128, 256, 512, 512)
+MIN_SIDE = {"alex": 31, "vgg": 16}                  # the last tap is 1 x 1 at this size
+LPIPS_SHIFT, LPIPS_SCALE = (-.030, -.088, -.188), (.458, .448, .450)
+DISTS_MEAN, DISTS_STD = (.485, .456, .406), (.229, .224, .225)
+# Live fp32 activations of one trunk group.  The peak of VGG16 is conv1_2: its 64-channel input and output at full resolution, next to the
+# 3-channel images (one 720 x 1280 stage-1 map is 236 MB); of AlexNet conv1's output at 1/16 of the pixels.  4 GiB holds four 720p pairs.
+ACTIVATION_BUDGET = 4 << 30
+FILE_PATTERNS = {"alex": "alexnet*.pth", "vgg": "vgg16*.pth", "lpips-alex": "LPIPS_v0.1_alex*.pth", "lpips-vgg": "LPIPS_v0.1_vgg*.pth",
+                 "dists": "DISTS_weights*.pth"}
+COUNTERS = {"groups": 0}                            # trunk groups walked, for tests and tools
+
+
+def backbone_param_shapes(net: str) -> dict:
+    """name -> shape of the conv entries of torchvision's ``alexnet`` / ``vgg16`` state dict that the metrics read."""
+    if net == "alex":
+        convs = [(n, cout, cin, k) for n, cout, cin, k, _, _ in ALEX_CONVS]
+    elif net == "vgg":
+        convs = [(n, cout, cin, 3) for stage in VGG_STAGES for n, cout, cin in stage]
+    else:
+        raise ValueError(f"net must be 'alex' or 'vgg', got {net!r}")
+    s = {}
+    for n, cout, cin, k in convs:
+        s[f"features.{n}.weight"] = (cout, cin, k, k)
+        s[f"features.{n}.bias"] = (cout,)
+    return s
+
+
+def _random_backbone(seed: int, net: str) -> dict:
+    out = {}
+    for name, shape in backbone_param_shapes(net).items():
+        rng = np.random.default_rng([int(seed), zlib.crc32(f"{net}.{name}".encode())])
+        v = rng.standard_normal(shape) * math.sqrt(2.0 / (shape[1] * shape[2] * shape[3])) if len(shape) == 4 else \
+            0.05 * rng.standard_normal(shape)
+        out[name] = torch.from_numpy(v.astype(np.float32))
+    return out
+
+
+def random_lpips_state(seed: int, net: str):
+    """Rule-generated (backbone_sd, lin_sd) for tests and tools: conv weights normal with He std, biases 0.05 * normal, lin uniform in
+    [0.05, 1]."""
+    lin = {}
+    for k, c in enumerate(LPIPS_CHANNELS[net]):
+        rng = np.random.default_rng([int(seed), zlib.crc32(f"{net}.lin{k}".encode())])
+        lin[f"lin{k}.model.1.weight"] = torch.from_numpy(rng.uniform(0.05, 1.0, (1, c, 1, 1)).astype(np.float32))
+    return _random_backbone(seed, net), lin
+
+
+def random_dists_state(seed: int):
+    """Rule-generated (backbone_sd, ab_sd): the VGG16 of ``random_lpips_state`` and alpha, beta uniform in [0.05, 1]."""
+    ab = {}
+    for name in ("alpha", "beta"):
+        rng = np.random.default_rng([int(seed), zlib.crc32(f"dists.{name}".encode())])
+        ab[name] = torch.from_numpy(rng.uniform(0.05, 1.0, (1, sum(DISTS_CHANNELS), 1, 1)).astype(np.float32))
+    return _random_backbone(seed, "vgg"), ab
+
+
+def _strip(sd: dict) -> dict:
+    if isinstance(sd, dict) and isinstance(sd.get("state_dict"), dict):
+        sd = sd["state_dict"]
+    return {(k[len("module."):] if k.startswith("module.") else k): v for k, v in sd.items()}
+
+
+def _checked(sd: dict, want: dict, what: str) -> dict:
+    for name, shape in want.items():
+        if name not in sd:
+            raise ValueError(f"{what}: {name} is missing (expected shape {tuple(shape)})")
+        if tuple(sd[name].shape) != tuple(shape):
+            raise ValueError(f"{what}: {name} has shape {tuple(sd[name].shape)}, expected {tuple(shape)}")
+    return sd
+
+
+def _pack_backbone(sd: dict, net: str) -> dict:
+    sd = _checked(_strip(sd), backbone_param_shapes(net), f"{'AlexNet' if net == 'alex' else 'VGG16'} checkpoint")
+    nums = [c[0] for c in ALEX_CONVS] if net == "alex" else [c[0] for stage in VGG_STAGES for c in stage]
+    return {n: (pack_conv_weight(sd[f"features.{n}.weight"]), sd[f"features.{n}.bias"].float().contiguous()) for n in nums}
+
+
+def _load_sd(path: str) -> dict:
+    return torch.load(path, map_location="cpu", weights_only=True)
+
+
+@dataclass
+class _Weights:
+    convs: dict = field(default_factory=dict)       # features.N -> (w [kh,kw,cin,cout], bias)
+    device: torch.device = torch.device("cpu")
+    _copies: dict = field(default_factory=dict, repr=False)      # device -> the copy made for it, so a metric uploads once
+
+    _TENSOR_LISTS = ()
+
+    def to(self, device):
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if device == self.device:
+            return self
+        if device not in self._copies:
+            new = type(self)(**{k: getattr(self, k) for k in self.__dataclass_fields__ if k != "_copies"})
+            new.convs = {n: (w.to(device), b.to(device)) for n, (w, b) in self.convs.items()}
+            for name in self._TENSOR_LISTS:
+                setattr(new, name, [t.to(device) for t in getattr(self, name)])
+            new.device = device
+            self._copies[device] = new
+        return self._copies[device]
+
+
+@dataclass
+class LpipsWeights(_Weights):
+    net: str = "alex"
+    lins: list = field(default_factory=list)        # five float32 [C]
+    _TENSOR_LISTS = ("lins",)
+
+    @classmethod
+    def from_state_dicts(cls, backbone_sd: dict, lin_sd: dict, net: str) -> "LpipsWeights":
+        convs = _pack_backbone(backbone_sd, net)
+        want = {f"lin{k}.model.1.weight": (1, c, 1, 1) for k, c in enumerate(LPIPS_CHANNELS[net])}
+        lin_sd = _checked(_strip(lin_sd), want, f"LPIPS v0.1 ({net}) linear layers")
+        return cls(convs=convs, net=net, lins=[lin_sd[name].float().reshape(-1).contiguous() for name in want])
+
+    @classmethod
+    def load(cls, backbone_path: str, lin_path: str, net: str) -> "LpipsWeights":
+        return cls.from_state_dicts(_load_sd(backbone_path), _load_sd(lin_path), net)
+
+
+@dataclass
+class DistsWeights(_Weights):
+    alpha: list = field(default_factory=list)       # six float64 [C], divided by sum(alpha) + sum(beta)
+    beta: list = field(default_factory=list)
+    _TENSOR_LISTS = ("alpha", "beta")
+
+    @classmethod
+    def from_state_dicts(cls, backbone_sd: dict, ab_sd: dict) -> "DistsWeights":
+        convs = _pack_backbone(backbone_sd, "vgg")
+        total = sum(DISTS_CHANNELS)
+        ab_sd = _checked(_strip(ab_sd), {"alpha": (1, total, 1, 1), "beta": (1, total, 1, 1)}, "DISTS weights")
+        a, b = ab_sd["alpha"].double().reshape(-1), ab_sd["beta"].double().reshape(-1)
+        w_sum = a.sum() + b.sum()
+        split = lambda t: [s.contiguous() for s in torch.split(t / w_sum, list(DISTS_CHANNELS))]
+        return cls(convs=convs, alpha=split(a), beta=split(b))
+
+    @classmethod
+    def load(cls, backbone_path: str, ab_path: str) -> "DistsWeights":
+        return cls.from_state_dicts(_load_sd(backbone_path), _load_sd(ab_path))
+
+
+def find_weight_file(directory: str, key: str) -> str:
+    """The file of ``FILE_PATTERNS[key]`` in ``directory`` (the names torchvision and pyiqa give their downloads)."""
+    hits = sorted(glob.glob(os.path.join(directory, FILE_PATTERNS[key])))
+    if not hits:
+        raise FileNotFoundError(f"no file matching {FILE_PATTERNS[key]} in {directory}")
+    return hits[0]
+
+
+def load_metric_weights(directory: str, name: str):
+    """Weights of metric ``name`` ('lpips', 'lpips-vgg', 'dists') from a directory of checkpoints."""
+    if name == "lpips":
+        return LpipsWeights.load(find_weight_file(directory, "alex"), find_weight_file(directory, "lpips-alex"), "alex")
+    if name == "lpips-vgg":
+        return LpipsWeights.load(find_weight_file(directory, "vgg"), find_weight_file(directory, "lpips-vgg"), "vgg")
+    if name == "dists":
+        return DistsWeights.load(find_weight_file(directory, "vgg"), find_weight_file(directory, "dists"))
+    raise ValueError(f"no network weights belong to metric {name!r}")
+
+
+# ------------------------------------------------------------------- walk -------------------------------------------------------------------
+def _inputs(pred: torch.Tensor, ref: torch.Tensor, net: str, what: str):
+    p, r = _as_nchw(pred, "auto"), _as_nchw(ref, "auto")
+    if p.shape != r.shape or p.shape[1] not in (1, 3):
+        raise ValueError(f"{what}: pred {tuple(pred.shape)} and ref {tuple(ref.shape)} must be the same [N,1|3,H,W] shape")
+    if min(p.shape[2:]) < MIN_SIDE[net]:
+        raise ValueError(f"{what}: images of {p.shape[2]} x {p.shape[3]} are too small; the minimum side is {MIN_SIDE[net]}")
+    if not (p.is_cuda and r.is_cuda) or p.device != r.device:
+        raise RuntimeError(f"{what} needs both images on the same HIP device (`cuda`); there is no CPU path")
+    fix = lambda t: t if t.dtype in (torch.uint8, torch.float32) else t.float()
+    return fix(p), fix(r)
+
+
+def group_size(net: str, h: int, w: int, budget: int | None = None) -> int:
+    """Frame pairs per trunk group: the most whose live activations (both images of each pair) stay under the budget, at least one."""
+    per_pixel = 4 * (3 + 3 + 64 + 64) if net == "vgg" else 4 * (3 + 8)
+    return max(1, int((ACTIVATION_BUDGET if budget is None else budget) // (2 * per_pixel * h * w)))
+
+
+def _conv(W, n: int, x: torch.Tensor, stride: int = 1, pad: int = 1) -> torch.Tensor:
+    w, b = W.convs[n]
+    return ops.convnet_conv_f32(x, w, b, stride=stride, pad=(pad, pad), relu=True)
+
+
+def _alex_taps(W, x):
+    for n, _, _, _, stride, pad in ALEX_CONVS:
+        if n in (3, 6):
+            x = ops.maxpool_f32(x, 3, 2)
+        x = _conv(W, n, x, stride, pad)
+        yield x
+
+
+def _vgg_taps(W, x, l2: bool):
+    for k, stage in enumerate(VGG_STAGES):
+        if k:
+            x = ops.l2pool_f32(x) if l2 else ops.maxpool_f32(x, 2, 2)
+        for n, _, _ in stage:
+            x = _conv(W, n, x)
+        yield x
+
+
+def _walk(W, pred, ref, net: str, what: str, group, per_group):
+    p, r = _inputs(pred, ref, net, what)
+    W = W.to(p.device)
+    N = p.shape[0]
+    out = torch.zeros(N, dtype=torch.float64, device=p.device)
+    g = group_size(net, p.shape[2], p.shape[3]) if group is None else max(1, int(group))
+    with torch.cuda.device(p.device):
+        for i in range(0, N, g):
+            per_group(W, p[i:i + g], r[i:i + g], out[i:i + g])
+            COUNTERS["groups"] += 1
+    return out
+
+
+def _prep_pair(p, r, pre_mul, pre_add, mean, std):
+    g, _, H, Wd = p.shape
+    x = torch.empty(2 * g, H, Wd, 3, dtype=torch.float32, device=p.device)
+    ops.percep_prep_f32(p, pre_mul, pre_add, mean, std, out=x[:g])
+    ops.percep_prep_f32(r, pre_mul, pre_add, mean, std, out=x[g:])
+    return x
+
+
+def lpips(W: LpipsWeights, pred: torch.Tensor, ref: torch.Tensor, group: int | None = None) -> torch.Tensor:
+    """LPIPS v0.1 per image -> float64 [N] on the device.  ``pred`` / ``ref``: [N,C,H,W] float in [0,1] or uint8 (any strides, C in
+    {1, 3}; one channel is repeated), or [F,H,W,3] uint8 frames.  ``group``: frame pairs per trunk batch (default: from the budget)."""
+
+    def per_group(Wd, p, r, out):
+        g = p.shape[0]
+        x = _prep_pair(p, r, 2.0, -1.0, LPIPS_SHIFT, LPIPS_SCALE)
+        taps = _alex_taps(Wd, x) if Wd.net == "alex" else _vgg_taps(Wd, x, False)
+        for lin, f in zip(Wd.lins, taps):
+            ops.lpips_layer(f[:g], f[g:], lin, out)
+
+    return _walk(W, pred, ref, W.net, "lpips", group, per_group)
+
+
+def dists(W: DistsWeights, pred: torch.Tensor, ref: torch.Tensor, group: int | None = None) -> torch.Tensor:
+    """DISTS per image -> float64 [N] on the device; inputs as for ``lpips``."""
+
+    def per_group(Wd, p, r, out):
+        g = p.shape[0]
+        raw = _prep_pair(p, r, 1.0, 0.0, (0.0, 0.0, 0.0), (1.0, 1.0, 1.0))
+        acc = torch.zeros(g, dtype=torch.float64, device=p.device)
+        ops.dists_layer(raw[:g], raw[g:], Wd.alpha[0], Wd.beta[0], acc)
+        del raw
+        x = _prep_pair(p, r, 1.0, 0.0, DISTS_MEAN, DISTS_STD)
+        for k, f in enumerate(_vgg_taps(Wd, x, True)):
+            ops.dists_layer(f[:g], f[g:], Wd.alpha[k + 1], Wd.beta[k + 1], acc)
+        out.copy_(1.0 - acc)
+
+    return _walk(W, pred, ref, "vgg", "dists", group, per_group)
+
+
+class PerceptualMetric(torch.nn.Module):
+    """pyiqa-style metric object for 'lpips', 'lpips-vgg' and 'dists': ``metric(pred, ref)`` with [N,C,H,W] images in [0,1] -> [N] fp64."""
+
+    lower_better = True
+
+    def __init__(self, name: str, weights):
+        super().__init__()
+        want = DistsWeights if name == "dists" else LpipsWeights
+        if not isinstance(weights, want) or (name != "dists" and weights.net != ("vgg" if name == "lpips-vgg" else "alex")):
+            raise TypeError(f"create_metric('{name}'): weights must be {want.__name__}" +
+                            ("" if name == "dists" else f" of net '{'vgg' if name == 'lpips-vgg' else 'alex'}'"))
+        self.metric_name, self.weights = name, weights
+        self.register_buffer("_anchor", torch.empty(0), persistent=False)
+
+    @property
+    def device(self) -> torch.device:
+        return self._anchor.device if self._anchor.is_cuda else torch.device("cuda", torch.cuda.current_device())
+
+    def forward(self, pred: torch.Tensor, ref: torch.Tensor) -> torch.Tensor:
+        if pred.dim() == 3:
+            pred, ref = pred[None], ref[None]
+        dev = self.device
+        self.weights = self.weights.to(dev)
+        fn = dists if self.metric_name == "dists" else lpips
+        return fn(self.weights, pred.to(dev), ref.to(dev))

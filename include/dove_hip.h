@@ -732,6 +732,52 @@ size_t dove_flow_warp_error_workspace_bytes(int n, int h, int w);
 int dove_flow_warp_error(const void* img1, const void* img2, int dtype, const float* flow_fw, const float* flow_bw, int n, int h, int w,
                          void* ws, size_t ws_bytes, double* out, float* warped, unsigned char* mask, void* stream);
 
+/* Perceptual metrics LPIPS and DISTS (csrc/percep.hip): the operators of a VGG16 / AlexNet trunk in exact fp32 and the two
+ * statistical heads in fp64.  Layouts and guarantees are those of the flow block: channels-last fp32 with pixel strides, no atomics, identical
+ * bits on repetition, and an image's result independent of the rest of the batch.
+ *   convnet_conv_f32: out = conv + bias, then max(., 0) if relu != 0.  kh, kw in 1..11, stride 1..4, pad_h < kh, pad_w < kw (zero padding),
+ *     ho = (h + 2 pad_h - kh) / stride + 1 >= 1; w is [kh][kw][cin][cout] fp32.  Each output is one fp32 FMA chain in K order (tap-major, then
+ *     channel), so on a shape dove_conv2d_f32 accepts the two give the same bits.  Two walks, chosen from the arguments alone and named by
+ *     dove_convnet_conv_f32_kernel_name ("" for arguments the call would refuse; needs no device): "convnet3x3_f32_kernel" for 3 x 3, stride 1,
+ *     pad 1, cin % 32 == 0, cout >= 128, cout % 4 == 0, ldx % 4 == 0 and 16-byte aligned x and w (a 128 x 128 tile, LDS double-buffered); "conv_f32_kernel"
+ *     (the flow block's kernel) otherwise.
+ *   percep_prep_f32: in is a strided view of n images of c in {1, 3} channels (DOVE_U8: value / 255; DOVE_F32: as is) -> out dense
+ *     [n][h][w][3] = (fma(pre_mul, v, pre_add) - mean[ch]) / std[ch]; a one-channel image feeds all three.  mean, std: host arrays of 3.
+ *   maxpool_f32: k x k window (1..4), stride s (1..4), no padding, ho = (h - k) / s + 1.  A NaN in a window is its result.
+ *   l2pool_f32: out = sqrt(sum_taps g x^2 + 1e-12) with g the 3 x 3 outer product of (1/4, 1/2, 1/4), stride 2, zero padding 1,
+ *     ho = (h - 1) / 2 + 1; summed in fp64, rounded once.
+ *   lpips_layer: x, y [n][h][w] pixels of stride ld, c channels.  Per pixel in fp64: nx = sqrt(sum_c x^2), ny likewise,
+ *     d = sum_c lin[c] (x / (nx + 1e-10) - y / (ny + 1e-10))^2; out[n] (fp64) += (sum over pixels of d) / (h w), one fp64 division.  Partials of 128 pixels, summed in a
+ *     fixed tree by a second launch.  ws: dove_lpips_layer_workspace_bytes.
+ *   dists_layer: per (n, c) in fp64 the means mx, my, the biased variances vx, vy and the covariance (1024-pixel two-pass partials merged in
+ *     slice order), then out[n] (fp64) += sum_c alpha[c] (2 mx my + 1e-6) / (mx^2 + my^2 + 1e-6) + beta[c] (2 cov + 1e-6) / (vx + vy + 1e-6).
+ *     alpha, beta: fp64 [c], already divided by the sum of all of them.  ws: dove_dists_layer_workspace_bytes.
+ *   The workspace sizes are 0 for an empty batch. */
+typedef struct dove_convnet_conv_f32_args {
+  unsigned int struct_size; /* = sizeof(dove_convnet_conv_f32_args) of the caller's header, as dove_conv_desc */
+  unsigned int reserved;    /* 0 */
+  const float* x;           /* [n][h][w_in] pixels of stride ldx, cin channels read */
+  const float* w;           /* [kh][kw][cin][cout] */
+  const float* bias;        /* [cout] or NULL */
+  float* out;               /* [n][ho][wo] pixels of stride ldo, cout channels written */
+  int n, h, w_in, cin, cout, kh, kw, stride, pad_h, pad_w;
+  int relu;
+  int reserved2;            /* 0 */
+  long long ldx, ldo;
+} dove_convnet_conv_f32_args;
+int dove_convnet_conv_f32(const dove_convnet_conv_f32_args* args, void* stream);
+const char* dove_convnet_conv_f32_kernel_name(const dove_convnet_conv_f32_args* args);
+int dove_percep_prep_f32(const dove_image_view* in, int n, int c, int h, int w, float pre_mul, float pre_add, const float* mean,
+                         const float* std, float* out, void* stream);
+int dove_maxpool_f32(const float* x, long long ldx, int n, int h, int w, int c, int k, int stride, float* out, long long ldo, void* stream);
+int dove_l2pool_f32(const float* x, long long ldx, int n, int h, int w, int c, float* out, long long ldo, void* stream);
+size_t dove_lpips_layer_workspace_bytes(int n, int h, int w);
+int dove_lpips_layer(const float* x, const float* y, long long ld, const float* lin, int n, int h, int w, int c, void* ws, size_t ws_bytes,
+                     double* out, void* stream);
+size_t dove_dists_layer_workspace_bytes(int n, int h, int w, int c);
+int dove_dists_layer(const float* x, const float* y, long long ld, const double* alpha, const double* beta, int n, int h, int w, int c, void* ws,
+                     size_t ws_bytes, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
