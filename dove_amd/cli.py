@@ -140,10 +140,11 @@ def main(argv=None):
     ap.add_argument("--input_json", type=str, default=None, help="{clip name: prompt}; clips without an entry use the empty prompt (ref :590-594, :676)")
     ap.add_argument("--output_path", type=str, default="./results")
     ap.add_argument("--gt_dir", type=str, default=None, help="ground-truth folders / .npy / .y4m clips for --eval_metrics (ref :511)")
-    ap.add_argument("--eval_metrics", type=str, default="", help="any of 'psnr,ssim' (ref :513), on the GPU; with --metric_weights also 'lpips,lpips-vgg,dists'; the other network metrics of pyiqa are not provided")
+    ap.add_argument("--eval_metrics", type=str, default="", help="any of 'psnr,ssim' (ref :513), on the GPU; with --metric_weights also 'lpips,lpips-vgg,dists' and the no-reference 'niqe' (which needs no --gt_dir); the other network metrics of pyiqa are not provided")
     ap.add_argument("--metric_weights", type=str, default="",
                     help="directory with the checkpoints of lpips / lpips-vgg / dists for --eval_metrics (alexnet*.pth, vgg16*.pth, "
-                         "LPIPS_v0.1_alex*.pth, LPIPS_v0.1_vgg*.pth, DISTS_weights*.pth; dove_amd.percep)")
+                         "LPIPS_v0.1_alex*.pth, LPIPS_v0.1_vgg*.pth, DISTS_weights*.pth; dove_amd.percep) and the model of niqe "
+                         "(niqe_modelparameters*.mat or niqe*.npz; dove_amd.niqe)")
     ap.add_argument("--png_save", action="store_true")
     ap.add_argument("--y4m_save", action="store_true",
                     help="write <clip>.y4m (YUV4MPEG2) with --fps and --save_format; with --chunk_len > 0 it is streamed chunk by chunk")
@@ -153,13 +154,14 @@ def main(argv=None):
     check_dtype(args)
     metrics = [m.strip().lower() for m in args.eval_metrics.split(",") if m.strip()]
     network = ("lpips", "lpips-vgg", "dists") if args.metric_weights else ()
-    if any(m not in ("psnr", "ssim") + network for m in metrics):
-        known = "'psnr', 'ssim', 'lpips', 'lpips-vgg' and 'dists'" if network else "'psnr' and 'ssim'"
+    no_ref = ("niqe",) if args.metric_weights else ()                     # no-reference: scored on the output alone
+    if any(m not in ("psnr", "ssim") + network + no_ref for m in metrics):
+        known = "'psnr', 'ssim', 'lpips', 'lpips-vgg', 'dists' and 'niqe'" if network else "'psnr' and 'ssim'"
         raise NotImplementedError(f"--eval_metrics {args.eval_metrics}: only {known} are computed here; " +
                                   ("the other pyiqa metrics are outside the path" if network else
                                    "the other pyiqa metrics need network weights and are outside the path "
-                                   "(--metric_weights DIR adds lpips, lpips-vgg and dists)"))
-    if metrics and not (args.gt_dir or args.eval_psnr_dir):
+                                   "(--metric_weights DIR adds lpips, lpips-vgg, dists and niqe)"))
+    if any(m not in no_ref for m in metrics) and not (args.gt_dir or args.eval_psnr_dir):
         raise ValueError(f"--eval_metrics {args.eval_metrics} needs --gt_dir")
     # with --eval_psnr_dir, PSNR stays on that flag's CPU path (against its folders, as before); the rest runs on the GPU against
     # --gt_dir (or the --eval_psnr_dir folders when --gt_dir is not given)
@@ -168,6 +170,9 @@ def main(argv=None):
     if args.metric_weights:
         from .percep import load_metric_weights
         metric_weights = {m: load_metric_weights(args.metric_weights, m) for m in metrics if m in network}
+        if "niqe" in metrics:
+            from .niqe import load_model
+            metric_weights["niqe"] = load_model(args.metric_weights)
     metrics_gt = args.gt_dir or args.eval_psnr_dir
     y4m_chroma = None
     if args.y4m_save:
@@ -248,9 +253,12 @@ def main(argv=None):
             psnrs[name] = float((10 * torch.log10(1.0 / (mse + 1e-8))).mean())
             print(f"[{name}] PSNR={psnrs[name]:.4f}")
         if gpu_metrics:
-            from .metrics import clip_metrics
-            gt = prepost.load_frames(os.path.join(metrics_gt, name), **yuv_in)
-            vals = clip_metrics(frames_out, gt, gpu_metrics, weights=metric_weights)
+            from .metrics import clip_metrics, nr_clip_metrics
+            if metrics_gt:
+                gt = prepost.load_frames(os.path.join(metrics_gt, name), **yuv_in)
+                vals = clip_metrics(frames_out, gt, gpu_metrics, weights=metric_weights)
+            else:                                                         # only no-reference metrics were asked for (checked above)
+                vals = nr_clip_metrics(frames_out, gpu_metrics, metric_weights)
             for m in gpu_metrics:
                 print(f"[{name}] {m.upper()}={vals[m]:.4f}")
         for m in metrics:

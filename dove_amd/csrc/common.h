@@ -61,6 +61,13 @@ struct PerDeviceOnce {
 
 __device__ __forceinline__ float bf2f(bf16_t v) { return __uint_as_float(((uint32_t)v) << 16); }
 
+// pyiqa's Y channel on data range 255 (rgb2yiq row 0): the luma of SSIM (metrics.hip) and NIQE (niqe.hip).  Evaluated in fp64 without
+// contraction, in the order written, so rint() sees the same value as a float64 restatement (ties included).
+__device__ __forceinline__ double luma255(double r, double g, double b) {
+#pragma clang fp contract(off)
+  return rint(255.0 * (0.299 * r + 0.587 * g + 0.114 * b));
+}
+
 // round-to-nearest-even, NaN preserved (same rounding as torch's float->bfloat16)
 __device__ __forceinline__ bf16_t f2bf(float f) {
   uint32_t u = __float_as_uint(f);

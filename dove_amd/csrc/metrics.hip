@@ -70,8 +70,7 @@ __device__ __forceinline__ double unit(uint32_t raw, int dtype, const double* u8
 
 // eval_metrics.py rgb_to_y: y = 0.257 r + 0.504 g + 0.098 b + 0.0625
 __device__ __forceinline__ double rgb_to_y(double r, double g, double b) { return 0.257 * r + 0.504 * g + 0.098 * b + 0.0625; }
-// pyiqa's Y channel on data range 255 (rgb2yiq row 0)
-__device__ __forceinline__ double luma255(double r, double g, double b) { return rint(255.0 * (0.299 * r + 0.587 * g + 0.114 * b)); }
+// pyiqa's Y channel on data range 255 (rgb2yiq row 0) is luma255() of common.h, shared with niqe.hip
 
 __device__ __forceinline__ double wave_sum_d(double v) {
 #pragma unroll

@@ -8,7 +8,10 @@ Inputs are PNG/JPG folders, single images, ``.npy`` clips (uint8 [F,H,W,3]) and 
 stream's range tag; dove_amd.y4m); mp4 decoding is not provided.  ``--metrics``
 defaults to ``psnr,ssim`` (the reference's default also lists clipiqa, which needs network weights).  ``--metric_weights DIR`` adds
 ``lpips``, ``lpips-vgg`` and ``dists`` from the checkpoints in that directory (dove_amd.percep); a file that is absent
-raises FileNotFoundError.  Without the flag a metric other than psnr / ssim fails to initialise with a message, as a pyiqa metric that
+raises FileNotFoundError.  The same directory holds the model of the no-reference ``niqe`` (``niqe_modelparameters*.mat``, then
+``niqe*.npz``; dove_amd.niqe).  Without ``--gt`` the no-reference metrics are computed on the predictions alone and
+written to the same JSON, as in the reference (its ``--gt`` is "optional for NR-IQA"); a clip is skipped only when no no-reference metric
+was asked for.  Without the flag a metric other than psnr / ssim fails to initialise with a message, as a pyiqa metric that
 cannot be created does in the reference."""
 from __future__ import annotations
 
@@ -69,12 +72,14 @@ def init_models(metrics, device=None, weights=None):
 
 
 def load_weights(metrics, directory):
-    """Weights of the network metrics among ``metrics`` from ``--metric_weights`` -> {metric: weights}; without a directory, none (the
+    """Weights of the network metrics and the NIQE model among ``metrics`` from ``--metric_weights`` -> {metric: weights}; without a directory, none (the
     metrics then fail to initialise, as before).  A file that is absent raises FileNotFoundError."""
     if not directory:
         return {}
-    from . import percep
-    return {m: percep.load_metric_weights(directory, m) for m in metrics if m in M.NETWORK_METRICS}
+    from . import niqe, percep
+    out = {m: percep.load_metric_weights(directory, m) for m in metrics if m in M.NETWORK_METRICS}
+    out.update({m: niqe.load_model(directory) for m in metrics if m in M.NR_METRICS})
+    return out
 
 
 def process(gt_root, pred_root, out_path, metrics, batch_mode=False, crop=0, test_y_channel=False, is_center=False,
@@ -92,8 +97,13 @@ def process(gt_root, pred_root, out_path, metrics, batch_mode=False, crop=0, tes
             print(f"Skipping {name}: no matching GT file.")
             continue
         try:
+            nr = [m for m in models if m in M.NR_METRICS]
             if gt_files is None:
-                print(f"Skipping {name}: GT is not provided and no NR-IQA metrics found.")
+                if not nr:
+                    print(f"Skipping {name}: GT is not provided and no NR-IQA metrics found.")
+                    continue
+                vals = M.nr_clip_metrics(load_sequence(pred_files[name]), nr, weights)
+                results[name] = {k: round(vals[k], 4) for k in nr}
                 continue
             pred = load_sequence(pred_files[name])
             gt = load_sequence(gt_files[name])
@@ -126,7 +136,7 @@ def process(gt_root, pred_root, out_path, metrics, batch_mode=False, crop=0, tes
 
 def main(argv=None):
     parser = argparse.ArgumentParser(description="PSNR / SSIM of SR results against ground truth on the GPU (dove_amd)")
-    parser.add_argument("--gt", type=str, default="", help="Path to GT folder")
+    parser.add_argument("--gt", type=str, default="", help="Path to GT folder (optional for the no-reference niqe)")
     parser.add_argument("--pred", type=str, required=True, help="Path to predicted results folder")
     parser.add_argument("--out", type=str, default="", help="Path to save JSON output (as directory); default: --pred")
     parser.add_argument("--metrics", type=str, default="psnr,ssim", help="Comma-separated list of metrics: psnr,ssim")
@@ -136,7 +146,8 @@ def main(argv=None):
     parser.add_argument("--is_center", action="store_true", help="Use center crop for PSNR/SSIM")
     parser.add_argument("--metric_weights", type=str, default="",
                         help="directory with the checkpoints of lpips / lpips-vgg / dists (alexnet*.pth, vgg16*.pth, LPIPS_v0.1_alex*.pth, "
-                             "LPIPS_v0.1_vgg*.pth, DISTS_weights*.pth); without it these metrics are not computed")
+                             "LPIPS_v0.1_vgg*.pth, DISTS_weights*.pth) and the model of niqe (niqe_modelparameters*.mat or niqe*.npz); "
+                             "without it these metrics are not computed")
     args = parser.parse_args(argv)
     out = args.out or args.pred
     metric_list = [m.strip().lower() for m in args.metrics.split(",")]

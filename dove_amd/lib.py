@@ -232,6 +232,10 @@ SIGNATURES = {
     "dove_l2pool_f32": [_VP, _LL, _I, _I, _I, _I, _VP, _LL, _VP],
     "dove_lpips_layer": [_VP, _VP, _LL, _VP, _I, _I, _I, _I, _VP, C.c_size_t, _VP, _VP],
     "dove_dists_layer": [_VP, _VP, _LL, _VP, _VP, _I, _I, _I, _I, _VP, C.c_size_t, _VP, _VP],
+    # NIQE (csrc/niqe.hip): features and stats on the device in fp64; the distance is host code on host pointers
+    "dove_niqe_features": [C.POINTER(ImageView), _I, _I, _I, _I, _VP, C.c_size_t, _VP, _VP, _VP],
+    "dove_niqe_stats": [_VP, _I, _I, _VP, _VP, _VP, _VP],
+    "dove_niqe_distance": [_VP, _VP, _VP, _VP, _VP],
 }
 PLAIN = {"dove_last_error": (C.c_char_p, []), "dove_abi_version": (C.c_int, []), "dove_comm_destroy": (None, [C.c_void_p]),
          "dove_conv_gn_partial_rows": (C.c_longlong, [C.POINTER(ConvDesc)]),
@@ -259,7 +263,8 @@ PLAIN = {"dove_last_error": (C.c_char_p, []), "dove_abi_version": (C.c_int, []),
          "dove_flow_warp_error_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
          "dove_convnet_conv_f32_kernel_name": (C.c_char_p, [C.POINTER(ConvnetConvF32Args)]),
          "dove_lpips_layer_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
-         "dove_dists_layer_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I])}
+         "dove_dists_layer_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I]),
+         "dove_niqe_workspace_bytes": (C.c_size_t, [_I, _I, _I])}
 
 
 def kernel_source_sha256() -> str:

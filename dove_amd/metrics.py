@@ -4,9 +4,11 @@ Three surfaces:
   - ``fr_metrics(pred, ref, psnr=True, ssim=True, rgb_to_y=False)``: per-image fp64 values of a batch of strided views;
   - ``create_metric(name)``: pyiqa's ``create_metric`` surface for 'psnr' and 'ssim', so the reference's metric code runs with
     ``import dove_amd.metrics as pyiqa``; ``create_metric(name, weights=W)`` gives 'lpips', 'lpips-vgg' and 'dists' from user-supplied
-    checkpoints (dove_amd.percep); any other name, or one of these without weights, raises ``NotImplementedError``;
+    checkpoints (dove_amd.percep) and the no-reference 'niqe' from a user-supplied pristine model (dove_amd.niqe.NiqeModel; called as
+    ``metric(pred)``); any other name, or one of these without weights, raises ``NotImplementedError``;
   - ``clip_metrics(pred_u8, gt_u8, names, crop, test_y_channel, is_center)``: the per-clip logic of eval_metrics.py (match_resolution,
-    crop_border, rgb_to_y, mean over frames), as views on the device.
+    crop_border, rgb_to_y, mean over frames), as views on the device; ``nr_clip_metrics(pred_u8, names, weights)`` is its ground-truth-free
+    half (the no-reference metrics on the predictions as they are).
 
 Definitions (pyiqa's 'psnr' / 'ssim' defaults, INTEGRATION.md 'Metrics'): values in [0,1], uint8 read as u/255.
 PSNR = 10 log10(1 / (mse + 1e-8)) over C, H, W.  SSIM on the luma Y = round(255 (0.299 R + 0.587 G + 0.114 B)) (round(255 v) for one
@@ -22,6 +24,7 @@ from . import ops
 
 FR_METRICS = ("psnr", "ssim")
 NETWORK_METRICS = ("lpips", "lpips-vgg", "dists")       # computed by dove_amd.percep when the caller passes weights
+NR_METRICS = ("niqe",)                                  # no-reference: computed by dove_amd.niqe when the caller passes a NiqeModel
 
 
 def _unsupported(name: str) -> NotImplementedError:
@@ -87,13 +90,17 @@ class FRMetric(torch.nn.Module):
 
 def create_metric(name: str, weights=None, **kwargs):
     """``pyiqa.create_metric`` for the full-reference metrics computed here: 'psnr' and 'ssim' with pyiqa's default options, and, given
-    ``weights`` (percep.LpipsWeights / percep.DistsWeights), 'lpips', 'lpips-vgg' and 'dists' (lower is better, [N] fp64)."""
+    ``weights`` (percep.LpipsWeights / percep.DistsWeights), 'lpips', 'lpips-vgg' and 'dists' (lower is better, [N] fp64); with
+    ``weights`` a niqe.NiqeModel, the no-reference 'niqe' (``metric(pred)``, lower is better, [N] fp64)."""
     key = name.strip().lower()
     if weights is not None:
-        if key not in NETWORK_METRICS:
-            raise NotImplementedError(f"create_metric('{name}', weights=...): weights belong to {', '.join(NETWORK_METRICS)}")
+        if key not in NETWORK_METRICS + NR_METRICS:
+            raise NotImplementedError(f"create_metric('{name}', weights=...): weights belong to {', '.join(NETWORK_METRICS + NR_METRICS)}")
         if kwargs:
             raise NotImplementedError(f"create_metric('{name}', {sorted(kwargs)}): only pyiqa's default options are implemented")
+        if key in NR_METRICS:
+            from . import niqe
+            return niqe.NiqeMetric(weights)
         from . import percep
         return percep.PerceptualMetric(key, weights)
     if key not in FR_METRICS:
@@ -106,6 +113,18 @@ def create_metric(name: str, weights=None, **kwargs):
 def list_models(metric_mode=None):
     """pyiqa.list_models: the metrics this module provides."""
     return list(FR_METRICS) if metric_mode in (None, "FR") else []
+
+
+def nr_clip_metrics(pred_u8: torch.Tensor, names, weights: dict) -> dict:
+    """Per-clip no-reference metrics -> {metric: mean over frames}.  The reference hands these the predictions as they are: no
+    match_resolution, no crop_border, no rgb_to_y.  ``pred_u8``: [F,H,W,3] uint8 frames (a host tensor is uploaded as uint8)."""
+    vals = {}
+    for n in names:
+        if n not in NR_METRICS or n not in weights:
+            raise _unsupported(n)
+        dev = pred_u8.device if pred_u8.is_cuda else torch.device("cuda")
+        vals[n] = float(create_metric(n, weights=weights[n])(pred_u8.to(dev).permute(0, 3, 1, 2)).mean())
+    return vals
 
 
 def _crop_hw(t: torch.Tensor, th: int, tw: int, is_center: bool) -> torch.Tensor:
@@ -142,7 +161,8 @@ def rgb_to_y(frames: torch.Tensor) -> torch.Tensor:
 
 def clip_metrics(pred_u8: torch.Tensor, gt_u8: torch.Tensor, names, crop: int = 0, test_y_channel: bool = False,
                  is_center: bool = False, name: str | None = None, weights: dict | None = None) -> dict:
-    """Per-clip full-reference metrics as eval_metrics.py computes them -> {metric: mean over frames of the per-frame value}.
+    """Per-clip metrics as eval_metrics.py computes them -> {metric: mean over frames of the per-frame value}: the full-reference ones,
+    and 'niqe' (given its model in ``weights``) on the uncropped predictions (``crop`` and ``test_y_channel`` do not apply to it).
 
     ``pred_u8`` / ``gt_u8``: [F,H,W,3] uint8 frames (a host tensor is uploaded as uint8).  Steps of the reference: match_resolution
     (common frame count, top-left or centre crop to the common H x W), crop_border, optional rgb_to_y; all of them are views."""
@@ -153,17 +173,19 @@ def clip_metrics(pred_u8: torch.Tensor, gt_u8: torch.Tensor, names, crop: int = 
             raise _unsupported(n)
     dev = pred_u8.device if pred_u8.is_cuda else (gt_u8.device if gt_u8.is_cuda else torch.device("cuda"))
     pred_u8, gt_u8 = pred_u8.to(dev), gt_u8.to(dev)
+    full = pred_u8                                              # the no-reference metrics see the predictions as they are
     gt, pred = match_resolution(gt_u8, pred_u8, is_center=is_center, name=name)
     gt, pred = crop_border(gt, crop), crop_border(pred, crop)
     vals = {}
     if "psnr" in names or "ssim" in names:
         vals["psnr"], vals["ssim"] = fr_metrics(pred, gt, psnr="psnr" in names, ssim="ssim" in names, rgb_to_y=test_y_channel,
                                                 layout="nhwc")
-    net = [n for n in names if n not in FR_METRICS]
+    nr = nr_clip_metrics(full, [n for n in names if n in NR_METRICS], weights)
+    net = [n for n in names if n not in FR_METRICS + NR_METRICS]
     if net:
         # the reference hands the networks the same cropped (and, with --test_y_channel, one-channel) images as PSNR / SSIM;
         # ``weights`` of a user-supplied checkpoint make the metric, so ``names`` without them were refused above
         p, g = (rgb_to_y(pred), rgb_to_y(gt)) if test_y_channel else (pred.permute(0, 3, 1, 2), gt.permute(0, 3, 1, 2))
         for n in net:
             vals[n] = create_metric(n, weights=weights[n])(p, g)
-    return {n: float(vals[n].mean()) for n in names}
+    return {n: nr[n] if n in nr else float(vals[n].mean()) for n in names}

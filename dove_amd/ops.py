@@ -666,6 +666,57 @@ def fr_metrics(pred: torch.Tensor, ref: torch.Tensor, flags: int) -> torch.Tenso
     return out
 
 
+def niqe_features(img: torch.Tensor):
+    """img: [N,C,H,W] view (any strides, no copy; uint8 / float32 / bfloat16, C in {1, 3}, H, W >= 96) -> (features fp64 [N,B,36],
+    sharpness fp64 [N,B]) on the device, B = (H // 96) * (W // 96) blocks in row-major order (csrc/niqe.hip)."""
+    if img.dim() != 4:
+        raise ValueError(f"niqe_features: expected an [N,C,H,W] view, got shape {tuple(img.shape)}")
+    if not img.is_cuda:
+        raise RuntimeError("niqe_features needs the images on the HIP device (`cuda`); there is no CPU path")
+    N, Cc, H, W = img.shape
+    if H < 96 or W < 96:
+        raise ValueError(f"niqe: H and W must be at least 96 (one 96 x 96 block), got {H} x {W}")
+    B = (H // 96) * (W // 96)
+    lib = L.load()
+    with torch.cuda.device(img.device):
+        ws = torch.empty(max(int(lib.dove_niqe_workspace_bytes(N, H, W)), 8), dtype=torch.uint8, device=img.device)
+        feats = torch.empty(N, B, 36, dtype=torch.float64, device=img.device)
+        sharp = torch.empty(N, B, dtype=torch.float64, device=img.device)
+        if N:
+            v = _image_view(img)
+            L.check(lib.dove_niqe_features(C.byref(v), N, Cc, H, W, L.ptr(ws), ws.numel(), L.ptr(feats), L.ptr(sharp), L.stream_ptr()),
+                    "dove_niqe_features")
+    return feats, sharp
+
+
+def niqe_stats(features: torch.Tensor):
+    """features: contiguous fp64 [N,B,36] on the device -> (mu fp64 [N,36], cov fp64 [N,36,36], counts int32 [N,2] = {blocks without a
+    NaN, blocks with at least one non-NaN feature})."""
+    if features.dim() != 3 or features.shape[2] != 36 or features.dtype != torch.float64 or features.shape[1] < 1:
+        raise ValueError(f"niqe_stats: expected float64 [N,B>=1,36], got {tuple(features.shape)} {features.dtype}")
+    L.require_cuda(features)
+    N, B, _ = features.shape
+    mu = torch.empty(N, 36, dtype=torch.float64, device=features.device)
+    cov = torch.empty(N, 36, 36, dtype=torch.float64, device=features.device)
+    counts = torch.empty(N, 2, dtype=torch.int32, device=features.device)
+    if N:
+        L.check(L.load().dove_niqe_stats(L.ptr(features), N, B, L.ptr(mu), L.ptr(cov), L.ptr(counts), L.stream_ptr()), "dove_niqe_stats")
+    return mu, cov, counts
+
+
+def niqe_distance(mu_a, cov_a, mu_b, cov_b) -> float:
+    """sqrt(d pinv((cov_a + cov_b) / 2) d^T), d = mu_a - mu_b, of two 36-feature Gaussian models given as HOST float64 arrays (host code
+    of the library: Jacobi eigen-solve, singular values at or below 36 eps sigma_max dropped).  NaN for a non-finite input."""
+    import numpy as np
+    arrs = [np.ascontiguousarray(np.asarray(a, dtype=np.float64)) for a in (mu_a, cov_a, mu_b, cov_b)]
+    for a, shape in zip(arrs, ((36,), (36, 36), (36,), (36, 36))):
+        if a.shape != shape:
+            raise ValueError(f"niqe_distance: expected shapes (36,), (36, 36), (36,), (36, 36), got {[x.shape for x in arrs]}")
+    out = C.c_double(0.0)
+    L.check(L.load().dove_niqe_distance(*(C.c_void_p(a.ctypes.data) for a in arrs), C.byref(out)), "dove_niqe_distance")
+    return out.value
+
+
 def color_fix(content: torch.Tensor, style: torch.Tensor, mode: int, out: torch.Tensor, clamp: bool = True,
               content_affine=(1.0, 0.0), style_affine=(1.0, 0.0)) -> torch.Tensor:
     """content, style, out: [N,3,H,W] views (any strides, no copy; float32 / bfloat16 / uint8) -> ``out`` filled with the colour fix of

@@ -778,6 +778,25 @@ size_t dove_dists_layer_workspace_bytes(int n, int h, int w, int c);
 int dove_dists_layer(const float* x, const float* y, long long ld, const double* alpha, const double* beta, int n, int h, int w, int c, void* ws,
                      size_t ws_bytes, double* out, void* stream);
 
+/* NIQE, the no-reference metric of the evaluation step (csrc/niqe.hip): pyiqa's 'niqe' with its defaults, all in fp64.
+ *   niqe_features: img is a strided view of n images of c in {1, 3} channels, h, w >= 96 (DOVE_U8: value / 255; DOVE_F32 / DOVE_BF16: values in
+ *     [0,1]).  The luma round(255 (0.299 R + 0.587 G + 0.114 B)) (round(255 v) for one channel) of the top-left (h/96)*96 x (w/96)*96 region is
+ *     cut into B = (h/96) (w/96) blocks, row-major.  features [n][B][36]: the 18 AGGD features of each 96 x 96 block, then the 18 of the
+ *     matching 48 x 48 block of the half-scale image; a product with an empty sign set has NaN features.  sharpness [n][B] (may be NULL): the
+ *     block's mean local deviation at scale 1.  ws: device scratch of dove_niqe_workspace_bytes(n, h, w) bytes (0 for an empty batch or
+ *     h, w < 96).  The first call on a device builds the Gamma tables on the host and uploads them (a blocking copy).
+ *   niqe_stats: features [n][blocks][36] -> mu [n][36], the mean of each column over its non-NaN entries (NaN for none); cov [n][36][36], the
+ *     covariance (divisor count - 1) over the blocks without a NaN (NaN for fewer than two); counts [n][2] (int) = {blocks without a NaN, blocks
+ *     with at least one non-NaN feature}.
+ *   niqe_distance: HOST code on HOST pointers, no device needed.  out = sqrt(d pinv((cov_a + cov_b) / 2) d^T), d = mu_a - mu_b, by a symmetric
+ *     Jacobi eigen-solve; pinv drops singular values at or below 36 eps sigma_max.  A non-finite input gives NaN, not an error.
+ *   No atomics: two calls give identical bits, and a frame's result does not depend on the rest of the batch. */
+size_t dove_niqe_workspace_bytes(int n, int h, int w);
+int dove_niqe_features(const dove_image_view* img, int n, int c, int h, int w, void* ws, size_t ws_bytes, double* features, double* sharpness,
+                       void* stream);
+int dove_niqe_stats(const double* features, int n, int blocks, double* mu, double* cov, int* counts, void* stream);
+int dove_niqe_distance(const double* mu_a, const double* cov_a, const double* mu_b, const double* cov_b, double* out);
+
 #ifdef __cplusplus
 }
 #endif
