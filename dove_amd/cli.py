@@ -153,9 +153,11 @@ def main(argv=None):
     args = ap.parse_args(argv)
     check_dtype(args)
     metrics = [m.strip().lower() for m in args.eval_metrics.split(",") if m.strip()]
-    network = ("lpips", "lpips-vgg", "dists") if args.metric_weights else ()
-    no_ref = ("niqe",) if args.metric_weights else ()                     # no-reference: scored on the output alone
-    if any(m not in ("psnr", "ssim") + network + no_ref for m in metrics):
+    from . import eval_metrics
+    from .metrics import FR_METRICS, NETWORK_METRICS, NR_METRICS
+    network = NETWORK_METRICS if args.metric_weights else ()
+    no_ref = NR_METRICS if args.metric_weights else ()                    # no-reference: scored on the output alone
+    if any(m not in FR_METRICS + network + no_ref for m in metrics):
         known = "'psnr', 'ssim', 'lpips', 'lpips-vgg', 'dists' and 'niqe'" if network else "'psnr' and 'ssim'"
         raise NotImplementedError(f"--eval_metrics {args.eval_metrics}: only {known} are computed here; " +
                                   ("the other pyiqa metrics are outside the path" if network else
@@ -166,13 +168,7 @@ def main(argv=None):
     # with --eval_psnr_dir, PSNR stays on that flag's CPU path (against its folders, as before); the rest runs on the GPU against
     # --gt_dir (or the --eval_psnr_dir folders when --gt_dir is not given)
     gpu_metrics = [m for m in metrics if not (m == "psnr" and args.eval_psnr_dir)]
-    metric_weights = {}
-    if args.metric_weights:
-        from .percep import load_metric_weights
-        metric_weights = {m: load_metric_weights(args.metric_weights, m) for m in metrics if m in network}
-        if "niqe" in metrics:
-            from .niqe import load_model
-            metric_weights["niqe"] = load_model(args.metric_weights)
+    metric_weights = eval_metrics.load_weights(metrics, args.metric_weights)
     metrics_gt = args.gt_dir or args.eval_psnr_dir
     y4m_chroma = None
     if args.y4m_save:
@@ -182,7 +178,7 @@ def main(argv=None):
         y4m_chroma = yuv.save_format_to_chroma(args.save_format)      # refused only where a Y4M file is written
 
     from . import prepost, tiling
-    from .inference import process_video
+    from .inference import run_clip
 
     pipe, emb = build_pipe(args)
     if args.y4m_save:
@@ -222,15 +218,11 @@ def main(argv=None):
                                       color_fix, need_frames)
         else:
             video, pad_f, pad_h, pad_w, orig = prepost.preprocess_frames(frames, args.upscale, upscale_mode=args.upscale_mode)
-            items = tiling.plan(video.shape, args.chunk_len, overlap_t, tuple(args.tile_size_hw), tuple(args.overlap_hw))
-            out = torch.zeros(video.shape, dtype=torch.bfloat16, device=video.device)
-            wc = torch.zeros(video.shape, dtype=torch.int32, device=video.device)
+            plan = dict(chunk_len=args.chunk_len, overlap_t=overlap_t, tile_size_hw=tuple(args.tile_size_hw), overlap_hw=tuple(args.overlap_hw))
             print(f"Process video: {name} | Prompt: {prompt} | Frame: {video.shape[2]} (ori: {orig[0]}; pad: {pad_f}) | Target Resolution: "
-                  f"{video.shape[3]}, {video.shape[4]} | Chunk Num: {len(items)}")
-            for (t0, t1, h0, h1, w0, w1), region in items:
-                piece = process_video(pipe, video[:, :, t0:t1, h0:h1, w0:w1], prompt=prompt, noise_step=args.noise_step,
-                                      sr_noise_step=args.sr_noise_step, empty_prompt_embedding=emb)
-                tiling.stitch(out, wc, piece, region)
+                  f"{video.shape[3]}, {video.shape[4]} | Chunk Num: {len(tiling.plan(video.shape, **plan))}")
+            out, wc = run_clip(pipe, video, prompt=prompt, noise_step=args.noise_step, sr_noise_step=args.sr_noise_step,
+                               empty_prompt_embedding=emb, out_device=video.device, out_dtype=torch.bfloat16, **plan)
             tiling.check_coverage(wc)
             if args.y4m_save:
                 frames_out = _save_clip_y4m(out, video, (pad_f, pad_h, pad_w), args, os.path.join(args.output_path, stem + ".y4m"),
@@ -270,7 +262,7 @@ def main(argv=None):
         average = {m: sum(v) / len(v) for m, v in scores.items()}
         for m in gpu_metrics:
             print(f"=== Overall Average {m.upper()}: {average[m]:.4f} ===")
-        with open(os.path.join(args.output_path, "metrics_" + "_".join(metrics) + ".json"), "w") as f:
+        with open(os.path.join(args.output_path, eval_metrics.output_name(metrics)), "w") as f:
             json.dump({"per_sample": scores, "average": average, "count": len(names)}, f, indent=2)
     print("All videos processed.")
 

@@ -32,7 +32,7 @@ import torch
 import torch.distributed as dist
 
 from . import tiling
-from .inference import process_video
+from .inference import process_video, run_clip
 from .vae import DiagonalGaussianDistribution, frame_batches
 
 
@@ -192,18 +192,12 @@ def run_clip_distributed(pipe, video, *, group=None, chunk_len=0, overlap_t=8, t
     stitched [1,3,F,H,W] fp32 host tensor (pieces are disjoint, so the merge is an all-reduce SUM) and the write
     count, on which the reference's exact-once coverage check is applied."""
     rank, world = dist.get_rank(group), dist.get_world_size(group)
-    items = tiling.plan(video.shape, chunk_len, overlap_t, tile_size_hw, overlap_hw)
-    out = torch.zeros(video.shape, dtype=torch.float32)
-    wc = torch.zeros(video.shape, dtype=torch.int32)
-    for i, ((t0, t1, h0, h1, w0, w1), region) in enumerate(items):
-        if not owns(i, len(items), rank, world):
-            continue
-        gen = None
-        if seeds is not None:   # per-item generator so the result does not depend on which rank ran the item
-            gen = torch.Generator(device=pipe.vae.device).manual_seed(int(seeds) + i)
-        piece = process_video(pipe, video[:, :, t0:t1, h0:h1, w0:w1], sr_noise_step=sr_noise_step,
-                              empty_prompt_embedding=empty_prompt_embedding, generator=gen)
-        tiling.stitch(out, wc, piece.float().cpu(), region)
+    gen = None
+    if seeds is not None:       # per-item generator so the result does not depend on which rank ran the item
+        gen = lambda i: torch.Generator(device=pipe.vae.device).manual_seed(int(seeds) + i)   # noqa: E731
+    out, wc = run_clip(pipe, video, chunk_len=chunk_len, overlap_t=overlap_t, tile_size_hw=tile_size_hw, overlap_hw=overlap_hw,
+                       empty_prompt_embedding=empty_prompt_embedding, sr_noise_step=sr_noise_step,
+                       work_filter=lambda i, n: owns(i, n, rank, world), generator=gen)
     backend = dist.get_backend(group)
     if backend == "nccl":
         dev = pipe.vae.device

@@ -76,17 +76,20 @@ def process_video(pipe, video: torch.Tensor, prompt: str = "", noise_step: int =
 @torch.no_grad()
 def run_clip(pipe, video: torch.Tensor, *, chunk_len: int = 0, overlap_t: int = 8, tile_size_hw=(0, 0), overlap_hw=(32, 32),
              empty_prompt_embedding=None, sr_noise_step: int = 399, noise_step: int = 0, work_filter=None,
-             generator=None) -> tuple:
-    """Chunk x tile loop + stitch of ref :682-729 on a pre-processed [1,3,F,H,W] clip in [-1,1].
-    ``work_filter(i, n)`` selects the work items this rank owns (multi-GPU chunk farm, dove_amd.dist).
-    Returns (output_video, write_count) on the host like the reference."""
+             generator=None, prompt: str = "", out_device="cpu", out_dtype=torch.float32) -> tuple:
+    """Chunk x tile loop + stitch of ref :682-729 on a pre-processed [1,3,F,H,W] clip in [-1,1]: the one such loop of the package
+    (dove_amd.cli and dove_amd.dist call it; dove_amd.stream runs its tile loop per chunk).
+    ``work_filter(i, n)`` selects the work items this rank owns (multi-GPU chunk farm, dove_amd.dist).  ``generator``: one
+    torch.Generator for every item, or a callable ``i -> Generator`` for one per item.
+    Returns (output_video, write_count) as ``out_dtype`` / int32 on ``out_device``: fp32 on the host like the reference by default.
+    The coverage check (``tiling.check_coverage``) is the caller's: a filtered rank has holes by design."""
     items = tiling.plan(video.shape, chunk_len, overlap_t, tile_size_hw, overlap_hw)
-    out = torch.zeros(video.shape, dtype=torch.float32)
-    wc = torch.zeros(video.shape, dtype=torch.int32)
+    out = torch.zeros(video.shape, dtype=out_dtype, device=out_device)
+    wc = torch.zeros(video.shape, dtype=torch.int32, device=out_device)
     for i, ((t0, t1, h0, h1, w0, w1), region) in enumerate(items):
         if work_filter is not None and not work_filter(i, len(items)):
             continue
-        piece = process_video(pipe, video[:, :, t0:t1, h0:h1, w0:w1], sr_noise_step=sr_noise_step, noise_step=noise_step,
-                              empty_prompt_embedding=empty_prompt_embedding, generator=generator)
-        tiling.stitch(out, wc, piece.float().cpu(), region)
+        piece = process_video(pipe, video[:, :, t0:t1, h0:h1, w0:w1], prompt=prompt, sr_noise_step=sr_noise_step, noise_step=noise_step,
+                              empty_prompt_embedding=empty_prompt_embedding, generator=generator(i) if callable(generator) else generator)
+        tiling.stitch(out, wc, piece.to(out.device), region)        # stitch casts to out's dtype (bf16 -> fp32 is exact on either side)
     return out, wc

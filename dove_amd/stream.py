@@ -126,6 +126,138 @@ def _log(msg: str):
     print(msg, file=sys.stderr, flush=True)
 
 
+def _geometry(reader, writer, upscale, chunk_len, overlap_t, yuv_matrix, yuv_range):
+    """What both streaming loops start from -> ((H, W, pad_h, pad_w), (Ho, Wo), in_fmt, out_fmt, ov_t, block).  ``in_fmt`` is None for
+    a reader of RGB frames; ``block`` is the number of frames the reader thread asks for at a time."""
+    H, W = reader.height, reader.width
+    in_fmt = yuvmod.format_of_reader(reader, yuv_matrix, yuv_range) if hasattr(reader, "chroma") else None
+    out_fmt = yuvmod.YuvFormat(writer.chroma, yuv_matrix, "full" if writer.full_range else "limited")
+    _, pad_h, pad_w = tiling.match_padding(1, H, W)
+    Ho, Wo = output_size(H, W, upscale)
+    if (writer.height, writer.width) != (Ho, Wo):
+        raise ValueError(f"the writer is {writer.width}x{writer.height}; {W}x{H} input at x{upscale} gives {Wo}x{Ho} frames")
+    ov_t = overlap_t if chunk_len > 0 else 0
+    block = max(chunk_len - ov_t, 1) if chunk_len > 0 else 32
+    return (H, W, pad_h, pad_w), (Ho, Wo), in_fmt, out_fmt, ov_t, block
+
+
+class _StreamIO:
+    """The threads and buffers around a streaming loop, as a context manager.  A reader thread prefetches blocks of frames into a bounded
+    queue; a writer thread writes from two pinned buffers, which D2H copies on a side stream fill.  Entering starts the threads; leaving
+    ends them, and their errors surface unless the body already failed."""
+
+    def __init__(self, reader, writer, block, dev, join_timeout):
+        self.reader, self.writer, self.block, self.dev, self.join_timeout = reader, writer, block, dev, join_timeout
+        self.stop = threading.Event()
+        self.in_q: queue.Queue = queue.Queue(maxsize=2)
+        self.out_q: queue.Queue = queue.Queue(maxsize=2)
+        self.free_q: queue.Queue = queue.Queue()
+        self.side = torch.cuda.Stream(device=dev)
+        self.pinned, self.keep = [None, None], [None, None]
+        for i in range(2):
+            self.free_q.put(i)
+        self.rd, self.wr = _Worker(self.read_loop, "dove-stream-reader"), _Worker(self.write_loop, "dove-stream-writer")
+
+    def put(self, q, item):
+        while not self.stop.is_set():
+            try:
+                q.put(item, timeout=_POLL)
+                return True
+            except queue.Full:
+                pass
+        return False
+
+    def read_loop(self):
+        while not self.stop.is_set():
+            blk = self.reader.read(self.block)
+            if blk.shape[0] and not self.put(self.in_q, blk):
+                return
+            if blk.shape[0] < self.block:
+                self.put(self.in_q, None)                           # end of the stream
+                return
+
+    def write_loop(self):
+        while True:
+            item = self.out_q.get()
+            if item is None:
+                return
+            i, k, event = item
+            event.synchronize()
+            self.writer.write(self.pinned[i][:k])
+            self.free_q.put(i)
+
+    def __enter__(self):
+        self.rd.start()
+        self.wr.start()
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        """End the reader and writer threads; their errors surface unless the run already failed."""
+        failed, rd, wr = exc_type is not None, self.rd, self.wr
+        self.stop.set()
+        while wr.is_alive():                                         # the sentinel goes in even when the queue is full of unwritten items
+            try:
+                self.out_q.put(None, timeout=_POLL)
+                break
+            except queue.Full:
+                if failed:
+                    try:
+                        self.out_q.get_nowait()
+                    except queue.Empty:
+                        pass
+        while rd.is_alive():                                         # a reader blocked on a full queue sees `stop` within _POLL
+            try:
+                self.in_q.get_nowait()
+            except queue.Empty:
+                pass
+            rd.join(_POLL)
+            if failed:
+                break                                                # it may be blocked in read() on a pipe: a daemon thread, not waited for
+        wr.join(self.join_timeout)
+        rd.join(_POLL if failed else self.join_timeout)
+        self.keep = [None, None]                # this object and its threads' targets form a cycle: device memory does not wait for the collector
+        hung = [t.name for t in (rd, wr) if t.is_alive()]
+        if not failed:
+            for t in (wr, rd):
+                if t.error is not None:
+                    raise t.error
+            if hung:
+                raise RuntimeError(f"threads still running after {self.join_timeout} s: {', '.join(hung)}")
+
+    def next_block(self):
+        """The next block of frames, None at the end of the stream."""
+        return _get(self.in_q, self.rd, "reader")
+
+    def acquire(self) -> int:
+        """Index of a pinned buffer; the writer hands a buffer back after its copy has completed."""
+        return _get(self.free_q, self.wr, "writer")
+
+    def release(self, i: int):
+        """Hand back an index that was acquired but not emitted."""
+        self.free_q.put(i)
+
+    def emit(self, i: int, payload: torch.Tensor, k: int, keep=None):
+        """Copy ``payload[:k]`` ([k, bytes] uint8 on the device) into pinned buffer ``i`` on the side stream and queue it for the writer."""
+        if self.pinned[i] is None or self.pinned[i].shape[0] < k:
+            self.pinned[i] = torch.empty(k, payload.shape[1], dtype=torch.uint8, pin_memory=True)
+        self.side.wait_stream(torch.cuda.current_stream(self.dev))
+        with torch.cuda.stream(self.side):
+            self.pinned[i][:k].copy_(payload[:k], non_blocking=True)
+            event = torch.cuda.Event()
+            event.record(self.side)
+        # ``keep`` lives until buffer i comes round again (two chunks later): its release then depends on the chunk order alone, not on
+        # when the side stream happened to finish
+        self.keep[i] = keep
+        while True:                                                  # a full queue stalls this thread, not the GPU
+            if self.wr.error is not None:
+                raise self.wr.error
+            try:
+                self.out_q.put((i, k, event), timeout=_POLL)
+                return
+            except queue.Full:
+                pass
+
+
 @torch.no_grad()
 def sr_stream(pipe, reader, writer, *, upscale: int = 4, upscale_mode: str = "bilinear", chunk_len: int = 0, overlap_t: int = 8,
               tile_size_hw=(0, 0), overlap_hw=(32, 32), noise_step: int = 0, sr_noise_step: int = 399, prompt: str = "",
@@ -138,16 +270,8 @@ def sr_stream(pipe, reader, writer, *, upscale: int = 4, upscale_mode: str = "bi
     ``output_size(height, width, upscale)``; its chroma layout and range, with ``yuv_matrix``, are the output format.
     Returns {"frames", "chunks", "pieces"}."""
     dev = pipe.vae.device
-    H, W = reader.height, reader.width
-    is_yuv = hasattr(reader, "chroma")
-    in_fmt = yuvmod.format_of_reader(reader, yuv_matrix, yuv_range) if is_yuv else None
-    out_fmt = yuvmod.YuvFormat(writer.chroma, yuv_matrix, "full" if writer.full_range else "limited")
-    _, pad_h, pad_w = tiling.match_padding(1, H, W)
+    (H, W, pad_h, pad_w), (Ho, Wo), in_fmt, out_fmt, ov_t, block = _geometry(reader, writer, upscale, chunk_len, overlap_t, yuv_matrix, yuv_range)
     Hs, Ws = (H + pad_h) * upscale, (W + pad_w) * upscale
-    Ho, Wo = output_size(H, W, upscale)
-    if (writer.height, writer.width) != (Ho, Wo):
-        raise ValueError(f"the writer is {writer.width}x{writer.height}; {W}x{H} input at x{upscale} gives {Wo}x{Ho} frames")
-    ov_t = overlap_t if chunk_len > 0 else 0
     ov_hw = tuple(overlap_hw) if tuple(tile_size_hw) != (0, 0) else (0, 0)
     tiles = tiling.make_spatial_tiles(Hs, Ws, tuple(tile_size_hw), ov_hw)
     planner = ChunkPlanner(chunk_len, ov_t)
@@ -155,58 +279,13 @@ def sr_stream(pipe, reader, writer, *, upscale: int = 4, upscale_mode: str = "bi
         log("[dove_amd.stream] --chunk_len 0 is one piece: the whole stream is read before anything is written (memory grows with the "
             "clip; set --chunk_len for bounded memory)")
 
-    # ---- reader thread: prefetches blocks of frames into a bounded queue ---------------------------------------------------------
-    stop = threading.Event()
-    block = max(chunk_len - ov_t, 1) if chunk_len > 0 else 32
-    in_q: queue.Queue = queue.Queue(maxsize=2)
-
-    def put(q, item):
-        while not stop.is_set():
-            try:
-                q.put(item, timeout=_POLL)
-                return True
-            except queue.Full:
-                pass
-        return False
-
-    def read_loop():
-        while not stop.is_set():
-            blk = reader.read(block)
-            if blk.shape[0] and not put(in_q, blk):
-                return
-            if blk.shape[0] < block:
-                put(in_q, None)                                     # end of the stream
-                return
-
-    # ---- writer thread: pinned double buffers, filled by D2H copies on a side stream --------------------------------------------
-    side = torch.cuda.Stream(device=dev)
-    out_q: queue.Queue = queue.Queue(maxsize=2)
-    free_q: queue.Queue = queue.Queue()
-    pinned, in_flight = [None, None], [None, None]
-    for i in range(2):
-        free_q.put(i)
-
-    def write_loop():
-        while True:
-            item = out_q.get()
-            if item is None:
-                return
-            i, k, event = item
-            event.synchronize()
-            writer.write(pinned[i][:k])
-            free_q.put(i)
-
-    rd, wr = _Worker(read_loop, "dove-stream-reader"), _Worker(write_loop, "dove-stream-writer")
     frames, base, total, eof, last_frame = [], 0, 0, False, None      # host frames [base, total) of the stream
     stats = {"frames": 0, "chunks": 0, "pieces": 0}
-    failed = False
-    rd.start()
-    wr.start()
-    try:
+    with _StreamIO(reader, writer, block, dev, join_timeout) as io:
         while True:
             need = planner.need()
             while not eof and (need is None or total < need):
-                blk = _get(in_q, rd, "reader")
+                blk = io.next_block()
                 if blk is None:
                     eof = True
                     break
@@ -225,7 +304,7 @@ def sr_stream(pipe, reader, writer, *, upscale: int = 4, upscale_mode: str = "bi
             t0, t1, last = chunk
             # the chunk's low-resolution frames; the padding repeats the last frame (tiling.match_padding)
             lr = torch.stack([frames[t - base] if t < total else last_frame for t in range(t0, t1)]).to(dev, non_blocking=True)
-            rgb = yuvmod.yuv_to_rgb(lr, H, W, in_fmt) if is_yuv else lr.contiguous()
+            rgb = yuvmod.yuv_to_rgb(lr, H, W, in_fmt) if in_fmt is not None else lr.contiguous()
             if upscale_mode == "bilinear":
                 video = ops.preprocess_u8(rgb, 0, pad_h, pad_w, upscale, torch.bfloat16)[None]
             else:
@@ -258,28 +337,10 @@ def sr_stream(pipe, reader, writer, *, upscale: int = 4, upscale_mode: str = "bi
                     del fixed, content, style
                 else:
                     payload = yuvmod.rgb_to_yuv(out[0, :, a:b], out_fmt, crop=(b - a, Ho, Wo))
-                k = b - a
-                i = _get(free_q, wr, "writer")                       # the writer hands a buffer back after its copy has completed
-                if pinned[i] is None or pinned[i].shape[0] < k:
-                    pinned[i] = torch.empty(k, payload.shape[1], dtype=torch.uint8, pin_memory=True)
-                side.wait_stream(torch.cuda.current_stream(dev))
-                with torch.cuda.stream(side):
-                    pinned[i][:k].copy_(payload, non_blocking=True)
-                    event = torch.cuda.Event()
-                    event.record(side)
-                # the device payload lives until its buffer comes round again (two chunks later): its release then depends on the chunk
-                # order alone, not on when the side stream happened to finish
-                in_flight[i] = payload
+                # the buffer is asked for only now, so that the GPU has worked on this chunk while the last one was being written
+                io.emit(io.acquire(), payload, b - a, keep=payload)
                 del payload
-                while True:                                          # a full queue stalls this thread, not the GPU
-                    if wr.error is not None:
-                        raise wr.error
-                    try:
-                        out_q.put((i, k, event), timeout=_POLL)
-                        break
-                    except queue.Full:
-                        pass
-                stats["frames"] += k
+                stats["frames"] += b - a
             del out, video
             stats["chunks"] += 1
             log(f"[dove_amd.stream] chunk {stats['chunks']}: frames {t0}..{t1 - 1}{' (last)' if last else ''}, "
@@ -290,11 +351,6 @@ def sr_stream(pipe, reader, writer, *, upscale: int = 4, upscale_mode: str = "bi
                 base += drop
             if last:
                 break
-    except BaseException:
-        failed = True
-        raise
-    finally:
-        _shutdown(stop, rd, wr, in_q, out_q, failed, join_timeout)
     writer.flush()
     return stats
 
@@ -343,15 +399,7 @@ def sr_stream_graph(ctx, scheduler, reader, writer, text, *, upscale: int = 4, c
     ``max_frames`` bounds the clip only with ``chunk_len == 0`` (one piece of the whole clip, sized when the session opens)."""
     from .graph import VideoSession
     dev = ctx.device
-    H, W = reader.height, reader.width
-    is_yuv = hasattr(reader, "chroma")
-    in_fmt = yuvmod.format_of_reader(reader, yuv_matrix, yuv_range) if is_yuv else None
-    out_fmt = yuvmod.YuvFormat(writer.chroma, yuv_matrix, "full" if writer.full_range else "limited")
-    Ho, Wo = output_size(H, W, upscale)
-    if (writer.height, writer.width) != (Ho, Wo):
-        raise ValueError(f"the writer is {writer.width}x{writer.height}; {W}x{H} input at x{upscale} gives {Wo}x{Ho} frames")
-    ov_t = overlap_t if chunk_len > 0 else 0
-    block = max(chunk_len - ov_t, 1) if chunk_len > 0 else 32
+    (H, W, pad_h, pad_w), _, in_fmt, out_fmt, _, block = _geometry(reader, writer, upscale, chunk_len, overlap_t, yuv_matrix, yuv_range)
     sa, s1 = scheduler._coeffs(torch.tensor([sr_noise_step]), torch.bfloat16)
     pre = (noise_step,) + tuple(scheduler._coeffs(torch.tensor([noise_step]), torch.bfloat16)) if noise_step else None
     if chunk_len == 0:
@@ -361,137 +409,44 @@ def sr_stream_graph(ctx, scheduler, reader, writer, text, *, upscale: int = 4, c
                         tile_size_hw=tuple(tile_size_hw), overlap_hw=tuple(overlap_hw), color_fix=color_fix, in_fmt=in_fmt, out_fmt=out_fmt,
                         noise_step=pre, seed=seed, max_frames=max_frames if chunk_len == 0 else 0, max_push=block)
 
-    # the reader / writer threads below are sr_stream's, kept beside it on purpose: sr_stream is pinned byte for byte by its own tests and is
-    # left as it was; only the shutdown (_shutdown) is shared
-    stop = threading.Event()
-    in_q: queue.Queue = queue.Queue(maxsize=2)
-
-    def put(q, item):
-        while not stop.is_set():
-            try:
-                q.put(item, timeout=_POLL)
-                return True
-            except queue.Full:
-                pass
-        return False
-
-    def read_loop():
-        while not stop.is_set():
-            blk = reader.read(block)
-            if blk.shape[0] and not put(in_q, blk):
-                return
-            if blk.shape[0] < block:
-                put(in_q, None)                                     # end of the stream
-                return
-
-    side = torch.cuda.Stream(device=dev)
-    out_q: queue.Queue = queue.Queue(maxsize=2)
-    free_q: queue.Queue = queue.Queue()
-    # a step's device payload lives until its pinned buffer comes round again (two chunks later), like sr_stream's
-    pinned, payloads = [None, None], [None, None]
-    for i in range(2):
-        free_q.put(i)
-
-    def write_loop():
-        while True:
-            item = out_q.get()
-            if item is None:
-                return
-            i, k, event = item
-            event.synchronize()
-            writer.write(pinned[i][:k])
-            free_q.put(i)
-
-    rd, wr = _Worker(read_loop, "dove-stream-reader"), _Worker(write_loop, "dove-stream-writer")
     stats = {"frames": 0, "chunks": 0, "pieces": 0}
-    total, eof, failed = 0, False, False
-    _, pad_h, pad_w = tiling.match_padding(1, H, W)
+    total, eof = 0, False
     n_tiles = len(tiling.make_spatial_tiles((H + pad_h) * upscale, (W + pad_w) * upscale, tuple(tile_size_hw),
                                             tuple(overlap_hw) if tuple(tile_size_hw) != (0, 0) else (0, 0)))
-    rd.start()
-    wr.start()
+    payloads = [None, None]                                          # one persistent device buffer per pinned buffer: a step writes into it
     try:
-        while not sess.done:
-            need = sess.need()
-            while not eof and (need is None or need > 0):
-                blk = _get(in_q, rd, "reader")
-                if blk is None:
-                    eof = True
-                    sess.end()
-                    break
-                sess.push(blk.to(dev, non_blocking=True))
-                total += blk.shape[0]
+        with _StreamIO(reader, writer, block, dev, join_timeout) as io:
+            while not sess.done:
                 need = sess.need()
-            if eof and total == 0:
-                raise ValueError("the input stream holds no frame")
-            i = _get(free_q, wr, "writer")                           # the writer hands a buffer back after its copy has completed
-            if payloads[i] is None:
-                payloads[i] = torch.empty(sess.max_step_frames, sess.out_frame_bytes, dtype=torch.uint8, device=dev)
-            got = sess.step(payloads[i])
-            k = got.shape[0]
-            stats["chunks"] += 1
-            stats["pieces"] += n_tiles
-            if k > 0:
-                if pinned[i] is None or pinned[i].shape[0] < k:
-                    pinned[i] = torch.empty(k, sess.out_frame_bytes, dtype=torch.uint8, pin_memory=True)
-                side.wait_stream(torch.cuda.current_stream(dev))
-                with torch.cuda.stream(side):
-                    pinned[i][:k].copy_(got, non_blocking=True)
-                    event = torch.cuda.Event()
-                    event.record(side)
-                while True:                                          # a full queue stalls this thread, not the GPU
-                    if wr.error is not None:
-                        raise wr.error
-                    try:
-                        out_q.put((i, k, event), timeout=_POLL)
+                while not eof and (need is None or need > 0):
+                    blk = io.next_block()
+                    if blk is None:
+                        eof = True
+                        sess.end()
                         break
-                    except queue.Full:
-                        pass
-                stats["frames"] += k
-            else:
-                free_q.put(i)
-            log(f"[dove_amd.stream] chunk {stats['chunks']}{' (last)' if sess.done else ''}: {stats['frames']} frames written")
-    except BaseException:
-        failed = True
-        raise
-    finally:
-        _shutdown(stop, rd, wr, in_q, out_q, failed, join_timeout)
+                    sess.push(blk.to(dev, non_blocking=True))
+                    total += blk.shape[0]
+                    need = sess.need()
+                if eof and total == 0:
+                    raise ValueError("the input stream holds no frame")
+                i = io.acquire()                                     # before the step: it writes into this index's device buffer
+                if payloads[i] is None:
+                    payloads[i] = torch.empty(sess.max_step_frames, sess.out_frame_bytes, dtype=torch.uint8, device=dev)
+                got = sess.step(payloads[i])
+                k = got.shape[0]
+                stats["chunks"] += 1
+                stats["pieces"] += n_tiles
+                if k > 0:
+                    io.emit(i, got, k)
+                    stats["frames"] += k
+                else:
+                    io.release(i)
+                log(f"[dove_amd.stream] chunk {stats['chunks']}{' (last)' if sess.done else ''}: {stats['frames']} frames written")
+    finally:                                                         # after the threads have ended
         torch.cuda.synchronize(dev)
         sess.close()
     writer.flush()
     return stats
-
-
-def _shutdown(stop, rd, wr, in_q, out_q, failed, join_timeout):
-    """End the reader and writer threads of a streaming run; their errors surface unless the run already failed."""
-    stop.set()
-    while wr.is_alive():                                             # the sentinel goes in even when the queue is full of unwritten items
-        try:
-            out_q.put(None, timeout=_POLL)
-            break
-        except queue.Full:
-            if failed:
-                try:
-                    out_q.get_nowait()
-                except queue.Empty:
-                    pass
-    while rd.is_alive():                                             # a reader blocked on a full queue sees `stop` within _POLL
-        try:
-            in_q.get_nowait()
-        except queue.Empty:
-            pass
-        rd.join(_POLL)
-        if failed:
-            break                                                    # it may be blocked in read() on a pipe: a daemon thread, not waited for
-    wr.join(join_timeout)
-    rd.join(_POLL if failed else join_timeout)
-    hung = [t.name for t in (rd, wr) if t.is_alive()]
-    if not failed:
-        for t in (wr, rd):
-            if t.error is not None:
-                raise t.error
-        if hung:
-            raise RuntimeError(f"threads still running after {join_timeout} s: {', '.join(hung)}")
 
 
 def main(argv=None):

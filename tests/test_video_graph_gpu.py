@@ -360,6 +360,55 @@ def test_errors_leave_the_context_usable(setup):
     assert got.tobytes() == want.tobytes()
 
 
+def test_streaming_errors_surface_and_threads_end(setup):
+    """tests/test_stream_gpu.py's test of the same name through ``stream.sr_stream_graph``: a broken output pipe, a truncated input and an
+    input without a frame end the run with their error, no worker thread stays behind, and the context computes what it computed."""
+    import io
+    import threading
+    import time
+
+    from dove_amd import stream, y4m
+
+    class Broken(io.BytesIO):
+        def write(self, b):
+            if self.tell() > 200:
+                raise BrokenPipeError(32, "Broken pipe")
+            return super().write(b)
+
+    def attempt(raw, sink):
+        reader = y4m.Y4MReader(io.BytesIO(raw))
+        writer = y4m.Y4MWriter(sink, UP * W, UP * H, 25, "420", False)
+        box = {}
+
+        def work():
+            try:
+                stream.sr_stream_graph(setup["ctx"], setup["sched"], reader, writer, setup["text"], upscale=UP, seed=SEED, log=lambda m: None,
+                                       **CHUNKED, **TILES)
+            except BaseException as e:                               # noqa: BLE001
+                box["error"] = e
+        before = threading.active_count()
+        t = threading.Thread(target=work, daemon=True)
+        t.start()
+        t.join(120)
+        assert not t.is_alive(), "sr_stream_graph hangs"
+        deadline = time.time() + 5
+        while threading.active_count() > before and time.time() < deadline:
+            time.sleep(0.05)
+        assert threading.active_count() <= before, "worker threads left behind"
+        got, _ = run_session(setup, data, **WHOLE, **ONE)             # and the context still computes what it computed
+        assert got.tobytes() == want.tobytes()
+        return box.get("error")
+
+    data = lr_rgb(9, seed=2)
+    want, _ = composition(setup, data, **WHOLE, **ONE)
+    clip = IN_HEADER + b"".join(b"FRAME\n" + fr.tobytes() for fr in lr_payload(26, seed=1))
+    assert isinstance(attempt(clip, Broken()), BrokenPipeError)
+    err = attempt(clip[:-100], io.BytesIO())
+    assert isinstance(err, ValueError) and "truncated" in str(err)
+    err = attempt(IN_HEADER, io.BytesIO())
+    assert isinstance(err, ValueError) and "no frame" in str(err)
+
+
 def test_stream_tool_with_graph_equals_the_session(golden_dir):
     """python -m dove_amd.stream --graph on a Y4M pipe: stdout is the Y4M stream of the in-process session on the same weights and seed."""
     import argparse
