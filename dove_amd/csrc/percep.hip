@@ -25,6 +25,8 @@
 
 int dove_conv_f32_general_launch(const float* x, const float* w, const float* bias, float* out, int n, int h, int w_in, int cin, int cout,
                                  int kh, int kw, int stride, int pad_h, int pad_w, int relu, long long ldx, long long ldo, void* stream);
+int dove_convnet3x3_fast_launch(const float* x, const float* w, const float* bias, float* out, int n, int h, int w_in, int cin, int cout,
+                                int relu, long long ldx, long long ldo, void* stream);
 
 namespace {
 
@@ -413,22 +415,29 @@ extern "C" const char* dove_convnet_conv_f32_kernel_name(const dove_convnet_conv
   return conv_is_fast(a) ? FAST_NAME : GENERAL_NAME;
 }
 
+// The fast walk on its own (clipiqa.hip checks the arguments of dove_resnet_conv_f32 by the rule of conv_is_fast before it calls this).
+__attribute__((visibility("hidden"))) int dove_convnet3x3_fast_launch(const float* x, const float* w, const float* bias, float* out, int n, int h,
+                                                                      int w_in, int cin, int cout, int relu, long long ldx, long long ldo,
+                                                                      void* stream) {
+  FastP p;
+  p.x = x; p.w = w; p.bias = bias; p.out = out;
+  p.H = h; p.W = w_in; p.Cin = cin; p.Cout = cout; p.relu = relu;
+  p.M = (long long)n * h * w_in; p.ldx = ldx; p.ldo = ldo;
+  static PerDeviceOnce attr_set;
+  if (auto once_ = attr_set.guard())
+    (void)hipFuncSetAttribute((const void*)convnet3x3_f32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, F_LDS);
+  dim3 grid((unsigned)((p.M + FM - 1) / FM), (unsigned)((cout + FN - 1) / FN), 1);
+  hipLaunchKernelGGL(convnet3x3_f32_kernel, grid, dim3(NT), F_LDS, (hipStream_t)stream, p);
+  DOVE_CHECK_LAUNCH("dove_convnet_conv_f32");
+  return DOVE_OK;
+}
+
 extern "C" int dove_convnet_conv_f32(const dove_convnet_conv_f32_args* a, void* stream) {
   if (!conv_args_ok(a, true)) return DOVE_EINVAL;
   if (!conv_is_fast(a))
     return dove_conv_f32_general_launch(a->x, a->w, a->bias, a->out, a->n, a->h, a->w_in, a->cin, a->cout, a->kh, a->kw, a->stride, a->pad_h,
                                         a->pad_w, a->relu, a->ldx, a->ldo, stream);
-  FastP p;
-  p.x = a->x; p.w = a->w; p.bias = a->bias; p.out = a->out;
-  p.H = a->h; p.W = a->w_in; p.Cin = a->cin; p.Cout = a->cout; p.relu = a->relu;
-  p.M = (long long)a->n * a->h * a->w_in; p.ldx = a->ldx; p.ldo = a->ldo;
-  static PerDeviceOnce attr_set;
-  if (auto once_ = attr_set.guard())
-    (void)hipFuncSetAttribute((const void*)convnet3x3_f32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, F_LDS);
-  dim3 grid((unsigned)((p.M + FM - 1) / FM), (unsigned)((a->cout + FN - 1) / FN), 1);
-  hipLaunchKernelGGL(convnet3x3_f32_kernel, grid, dim3(NT), F_LDS, (hipStream_t)stream, p);
-  DOVE_CHECK_LAUNCH("dove_convnet_conv_f32");
-  return DOVE_OK;
+  return dove_convnet3x3_fast_launch(a->x, a->w, a->bias, a->out, a->n, a->h, a->w_in, a->cin, a->cout, a->relu, a->ldx, a->ldo, stream);
 }
 
 extern "C" int dove_percep_prep_f32(const dove_image_view* in, int n, int c, int h, int w, float pre_mul, float pre_add, const float* mean,

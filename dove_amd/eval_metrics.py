@@ -6,10 +6,11 @@ ground truth by ``os.path.splitext`` stem, the same per-clip steps (match_resolu
 same JSON (``metrics_<names>.json``: per_sample {clip: {metric: round(value, 4)}}, average of the rounded values, count).
 Inputs are PNG/JPG folders, single images, ``.npy`` clips (uint8 [F,H,W,3]) and ``.y4m`` files (YUV4MPEG2, read as bt601 with the
 stream's range tag; dove_amd.y4m); mp4 decoding is not provided.  ``--metrics``
-defaults to ``psnr,ssim`` (the reference's default also lists clipiqa, which needs network weights).  ``--metric_weights DIR`` adds
+defaults to ``psnr,ssim`` (the reference's default also lists clipiqa, which needs ``--metric_weights``).  ``--metric_weights DIR`` adds
 ``lpips``, ``lpips-vgg`` and ``dists`` from the checkpoints in that directory (dove_amd.percep); a file that is absent
 raises FileNotFoundError.  The same directory holds the model of the no-reference ``niqe`` (``niqe_modelparameters*.mat``, then
-``niqe*.npz``; dove_amd.niqe).  Without ``--gt`` the no-reference metrics are computed on the predictions alone and
+``niqe*.npz``; dove_amd.niqe, INTEGRATION.md 1i) and the files of the no-reference ``clipiqa`` (``RN50*.pt`` and ``clipiqa_text*.npz``;
+dove_amd.clipiqa).  Without ``--gt`` the no-reference metrics are computed on the predictions alone and
 written to the same JSON, as in the reference (its ``--gt`` is "optional for NR-IQA"); a clip is skipped only when no no-reference metric
 was asked for.  Without the flag a metric other than psnr / ssim fails to initialise with a message, as a pyiqa metric that
 cannot be created does in the reference."""
@@ -76,9 +77,10 @@ def load_weights(metrics, directory):
     metrics then fail to initialise, as before).  A file that is absent raises FileNotFoundError."""
     if not directory:
         return {}
-    from . import niqe, percep
+    from . import clipiqa, niqe, percep
+    loaders = {"niqe": niqe.load_model, "clipiqa": clipiqa.ClipIqaWeights.load}
     out = {m: percep.load_metric_weights(directory, m) for m in metrics if m in M.NETWORK_METRICS}
-    out.update({m: niqe.load_model(directory) for m in metrics if m in M.NR_METRICS})
+    out.update({m: loaders[m](directory) for m in metrics if m in M.NR_METRICS})
     return out
 
 
@@ -136,7 +138,7 @@ def process(gt_root, pred_root, out_path, metrics, batch_mode=False, crop=0, tes
 
 def main(argv=None):
     parser = argparse.ArgumentParser(description="PSNR / SSIM of SR results against ground truth on the GPU (dove_amd)")
-    parser.add_argument("--gt", type=str, default="", help="Path to GT folder (optional for the no-reference niqe)")
+    parser.add_argument("--gt", type=str, default="", help="Path to GT folder (optional for the no-reference niqe and clipiqa)")
     parser.add_argument("--pred", type=str, required=True, help="Path to predicted results folder")
     parser.add_argument("--out", type=str, default="", help="Path to save JSON output (as directory); default: --pred")
     parser.add_argument("--metrics", type=str, default="psnr,ssim", help="Comma-separated list of metrics: psnr,ssim")
@@ -146,7 +148,8 @@ def main(argv=None):
     parser.add_argument("--is_center", action="store_true", help="Use center crop for PSNR/SSIM")
     parser.add_argument("--metric_weights", type=str, default="",
                         help="directory with the checkpoints of lpips / lpips-vgg / dists (alexnet*.pth, vgg16*.pth, LPIPS_v0.1_alex*.pth, "
-                             "LPIPS_v0.1_vgg*.pth, DISTS_weights*.pth) and the model of niqe (niqe_modelparameters*.mat or niqe*.npz); "
+                             "LPIPS_v0.1_vgg*.pth, DISTS_weights*.pth), the model of niqe (niqe_modelparameters*.mat or niqe*.npz) and the files of "
+                             "clipiqa (RN50*.pt, clipiqa_text*.npz); "
                              "without it these metrics are not computed")
     args = parser.parse_args(argv)
     out = args.out or args.pred

@@ -115,6 +115,19 @@ class ConvnetConvF32Args(C.Structure):
         self.struct_size = C.sizeof(ConvnetConvF32Args)
 
 
+class ResnetConvF32Args(C.Structure):
+    """dove_resnet_conv_f32_args (include/dove_hip.h).  ``struct_size`` is filled in on construction, like ConvDesc."""
+    _fields_ = [("struct_size", C.c_uint), ("reserved", C.c_uint),
+                ("x", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("residual", C.c_void_p), ("out", C.c_void_p),
+                ("n", C.c_int), ("h", C.c_int), ("w_in", C.c_int), ("cin", C.c_int), ("cout", C.c_int), ("k", C.c_int),
+                ("stride", C.c_int), ("pool", C.c_int), ("relu", C.c_int), ("reserved2", C.c_int),
+                ("ldx", C.c_longlong), ("ldr", C.c_longlong), ("ldo", C.c_longlong)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size = C.sizeof(ResnetConvF32Args)
+
+
 class PreNoise(C.Structure):
     """dove_pre_noise: `--noise_step` of the graph-level dove_sr_clip."""
     _fields_ = [("eps", C.c_void_p), ("eps_dtype", C.c_int), ("sqrt_alpha", C.c_float), ("sqrt_one_minus_alpha", C.c_float)]
@@ -236,6 +249,11 @@ SIGNATURES = {
     "dove_niqe_features": [C.POINTER(ImageView), _I, _I, _I, _I, _VP, C.c_size_t, _VP, _VP, _VP],
     "dove_niqe_stats": [_VP, _I, _I, _VP, _VP, _VP, _VP],
     "dove_niqe_distance": [_VP, _VP, _VP, _VP, _VP],
+    # CLIP-IQA (csrc/clipiqa.hip): the fp32 ResNet operators, the attention pool and the score in fp64
+    "dove_resnet_conv_f32": [C.POINTER(ResnetConvF32Args), _VP],
+    "dove_avgpool_cl_f32": [_VP, _LL, _I, _I, _I, _I, _VP, _LL, _VP],
+    "dove_clip_attnpool_f32": [_VP, _LL, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP, _VP],
+    "dove_clipiqa_score": [_VP, _VP, _I, _I, _I, C.c_double, _VP, _VP],
 }
 PLAIN = {"dove_last_error": (C.c_char_p, []), "dove_abi_version": (C.c_int, []), "dove_comm_destroy": (None, [C.c_void_p]),
          "dove_conv_gn_partial_rows": (C.c_longlong, [C.POINTER(ConvDesc)]),
@@ -264,7 +282,9 @@ PLAIN = {"dove_last_error": (C.c_char_p, []), "dove_abi_version": (C.c_int, []),
          "dove_convnet_conv_f32_kernel_name": (C.c_char_p, [C.POINTER(ConvnetConvF32Args)]),
          "dove_lpips_layer_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
          "dove_dists_layer_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I]),
-         "dove_niqe_workspace_bytes": (C.c_size_t, [_I, _I, _I])}
+         "dove_niqe_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
+         "dove_resnet_conv_f32_kernel_name": (C.c_char_p, [C.POINTER(ResnetConvF32Args)]),
+         "dove_clip_attnpool_workspace_bytes": (C.c_size_t, [_I, _I, _I])}
 
 
 def kernel_source_sha256() -> str:

@@ -1237,3 +1237,102 @@ def dists_layer(x: torch.Tensor, y: torch.Tensor, alpha: torch.Tensor, beta: tor
     L.check(lib.dove_dists_layer(L.ptr(x), L.ptr(y), ld, L.ptr(alpha), L.ptr(beta), N, H, W, Cc, L.ptr(ws), ws.numel(), L.ptr(out),
                                  L.stream_ptr()), "dove_dists_layer")
     return out
+
+
+# ---- CLIP-IQA (csrc/clipiqa.hip): the fp32 operators of CLIP RN50's ResNet, its attention pool and the prompt-pair score ------------------
+def _resnet_args(x_shape, ldx: int, w_shape, stride: int, pool: int, relu: bool, ldo: int | None = None) -> "L.ResnetConvF32Args":
+    N, H, W, cin = x_shape
+    k, _, _, cout = w_shape
+    a = L.ResnetConvF32Args()
+    a.n, a.h, a.w_in, a.cin, a.cout, a.k, a.stride, a.pool, a.relu = N, H, W, cin, cout, k, stride, pool, int(relu)
+    a.ldx, a.ldo = ldx, cout if ldo is None else ldo
+    return a
+
+
+def resnet_conv_kernel_name(x_shape, w_shape, stride: int = 1, pool: int = 1, ldx: int | None = None) -> str:
+    """The kernel ``resnet_conv_f32`` runs for dense, aligned tensors of these shapes ('' for a shape it refuses); needs no device."""
+    a = _resnet_args(x_shape, x_shape[3] if ldx is None else ldx, w_shape, stride, pool, True)
+    a.x = a.w = a.out = 256                                            # placeholders: only their alignment is looked at
+    return L.load().dove_resnet_conv_f32_kernel_name(C.byref(a)).decode()
+
+
+def resnet_conv_f32(x: torch.Tensor, w: torch.Tensor, bias=None, *, stride: int = 1, pool: int = 1, residual: torch.Tensor | None = None,
+                    relu: bool = True, out: torch.Tensor | None = None, want_name: bool = False):
+    """x [N,H,W,Cin] (a channel slice is fine), w float32 [k,k,Cin,Cout], k in {1, 3} with padding k // 2 -> out [N,Ho,Wo,Cout] =
+    relu?((conv + bias) + residual).  ``pool`` 2: the conv reads the 2 x 2 average of x (floor sizes); it and ``residual`` belong to the
+    1 x 1 convs that run on pointwise_f32_kernel.  ``residual`` and ``out`` may be channel slices, and may be one tensor.
+    ``want_name``: also return the kernel that ran."""
+    ldx = _cl_f32(x, "resnet_conv_f32 x")
+    L.require_cuda(w, bias)
+    N, H, W, cin = x.shape
+    if w.dtype != torch.float32 or w.dim() != 4 or w.shape[2] != cin or w.shape[0] != w.shape[1] or w.shape[0] not in (1, 3):
+        raise ValueError(f"resnet_conv_f32: w {tuple(w.shape)} {w.dtype} must be float32 [k,k,{cin},Cout] with k 1 or 3")
+    k, _, _, cout = w.shape
+    if bias is not None and (bias.dtype != torch.float32 or bias.numel() != cout):
+        raise ValueError(f"resnet_conv_f32: bias must be float32 [{cout}]")
+    if pool not in (1, 2) or stride not in (1, 2):
+        raise ValueError(f"resnet_conv_f32: pool {pool} and stride {stride} must be 1 or 2")
+    ho, wo = (H // pool + 2 * (k // 2) - k) // stride + 1, (W // pool + 2 * (k // 2) - k) // stride + 1
+    if ho < 1 or wo < 1:
+        raise ValueError(f"resnet_conv_f32: image {H} x {W} is too small for pool {pool}")
+    if out is None:
+        out = torch.empty(N, ho, wo, cout, dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != (N, ho, wo, cout):
+        raise ValueError(f"resnet_conv_f32: out {tuple(out.shape)} must be {(N, ho, wo, cout)}")
+    a = _resnet_args(x.shape, ldx, w.shape, stride, pool, relu, _cl_f32(out, "resnet_conv_f32 out"))
+    a.x, a.w, a.out = x.data_ptr(), w.data_ptr(), out.data_ptr()
+    a.bias = bias.data_ptr() if bias is not None else None
+    if residual is not None:
+        if tuple(residual.shape) != (N, ho, wo, cout):
+            raise ValueError(f"resnet_conv_f32: residual {tuple(residual.shape)} must be {(N, ho, wo, cout)}")
+        a.ldr, a.residual = _cl_f32(residual, "resnet_conv_f32 residual"), residual.data_ptr()
+    lib = L.load()
+    L.check(lib.dove_resnet_conv_f32(C.byref(a), L.stream_ptr()), "dove_resnet_conv_f32")
+    return (out, lib.dove_resnet_conv_f32_kernel_name(C.byref(a)).decode()) if want_name else out
+
+
+def avgpool_cl_f32(x: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """2 x 2, stride 2 average of float32 [N,H,W,C] (a channel slice is fine), floor sizes: ((a + b) + (c + d)) * 0.25 in fp32."""
+    ldx = _cl_f32(x, "avgpool_cl_f32 x")
+    N, H, W, Cc = x.shape
+    if H < 2 or W < 2:
+        raise ValueError(f"avgpool_cl_f32: image {H} x {W} is smaller than the window 2")
+    if out is None:
+        out = torch.empty(N, H // 2, W // 2, Cc, dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != (N, H // 2, W // 2, Cc):
+        raise ValueError(f"avgpool_cl_f32: out {tuple(out.shape)} must be {(N, H // 2, W // 2, Cc)}")
+    L.check(L.load().dove_avgpool_cl_f32(L.ptr(x), ldx, N, H, W, Cc, L.ptr(out), _cl_f32(out, "avgpool_cl_f32 out"), L.stream_ptr()),
+            "dove_avgpool_cl_f32")
+    return out
+
+
+def clip_attnpool_f32(x: torch.Tensor, proj) -> torch.Tensor:
+    """x float32 [N,H,W,2048] feature map, ``proj`` = (wq, bq, wk, bk, wv, bv, wc, bc) float32 as torch holds them ([out,in] weights) ->
+    float32 [N,1024]: CLIP's attention pool without the positional embedding, evaluated in fp64 with the mean token as the only query."""
+    ldx = _cl_f32(x, "clip_attnpool_f32 x")
+    N, H, W, Cc = x.shape
+    proj = tuple(proj)
+    L.require_cuda(*proj)
+    want = [(2048, 2048), (2048,)] * 3 + [(1024, 2048), (1024,)]
+    if Cc != 2048 or len(proj) != 8 or any(t.dtype != torch.float32 or tuple(t.shape) != s for t, s in zip(proj, want)):
+        raise ValueError(f"clip_attnpool_f32: x must have 2048 channels (got {Cc}) and proj must be float32 tensors of shapes {want}")
+    lib = L.load()
+    ws = torch.empty(max(int(lib.dove_clip_attnpool_workspace_bytes(N, H, W)), 8), dtype=torch.uint8, device=x.device)
+    out = torch.empty(N, 1024, dtype=torch.float32, device=x.device)
+    L.check(lib.dove_clip_attnpool_f32(L.ptr(x), ldx, N, H, W, *[L.ptr(t) for t in proj], L.ptr(ws), ws.numel(), L.ptr(out), L.stream_ptr()),
+            "dove_clip_attnpool_f32")
+    return out
+
+
+def clipiqa_score(emb: torch.Tensor, text: torch.Tensor, logit_scale: float) -> torch.Tensor:
+    """emb float32 [N,D], text float64 [2P,D] (L2-normalised rows, positive then negative of each pair), ``logit_scale`` = exp of CLIP's
+    parameter -> float64 [N]: the mean over the pairs of softmax(logit_scale * emb / |emb| . text_pair)[0], in fp64."""
+    L.require_cuda(emb, text)
+    if emb.dtype != torch.float32 or emb.dim() != 2 or text.dtype != torch.float64 or text.dim() != 2 or text.shape[1] != emb.shape[1] or \
+            text.shape[0] < 2 or text.shape[0] % 2:
+        raise ValueError(f"clipiqa_score: emb {tuple(emb.shape)} {emb.dtype} must be float32 [N,D] and text {tuple(text.shape)} {text.dtype} "
+                         "float64 [2P,D]")
+    out = torch.empty(emb.shape[0], dtype=torch.float64, device=emb.device)
+    L.check(L.load().dove_clipiqa_score(L.ptr(emb), L.ptr(text), emb.shape[0], text.shape[0] // 2, emb.shape[1], float(logit_scale), L.ptr(out),
+                                        L.stream_ptr()), "dove_clipiqa_score")
+    return out

@@ -797,6 +797,50 @@ int dove_niqe_features(const dove_image_view* img, int n, int c, int h, int w, v
 int dove_niqe_stats(const double* features, int n, int blocks, double* mu, double* cov, int* counts, void* stream);
 int dove_niqe_distance(const double* mu_a, const double* cov_a, const double* mu_b, const double* cov_b, double* out);
 
+/* CLIP-IQA (csrc/clipiqa.hip): the operators of CLIP RN50's ModifiedResNet in exact fp32, its attention pool and the
+ * prompt-pair score in fp64.  Layouts and guarantees are those of the perceptual block: channels-last fp32 with pixel strides, weights
+ * [k][k][cin][cout] (BatchNorm folded in by the host), no atomics, identical bits on repetition, an image's result independent of the batch.
+ *   resnet_conv_f32: out = relu?((conv + bias) + residual).  k in {1, 3} with zero padding k / 2, stride in {1, 2}; pool in {1, 2}: with 2 the
+ *     conv reads the 2 x 2 average ((a + b) + (c + d)) * 0.25f of its input (floor sizes; a, b the upper pixels), so ho = h / 2.  Each output
+ *     is one fp32 FMA chain in K order (tap-major, then channel): the bits are dove_convnet_conv_f32's.  Four walks, chosen from the arguments
+ *     alone and named by dove_resnet_conv_f32_kernel_name ("" for arguments the call would refuse; needs no device):
+ *       "pointwise_f32_kernel": k 1, stride 1, cin % 32 == 0, cout % 4 == 0, ldx % 4 == 0, 16-byte aligned x and w (a 128 x 128 tile, 128 x 64
+ *         for cout < 128, LDS double-buffered).  The only walk with pool 2 and with a residual: both are refused on any other.
+ *       "convnet3x3_n64_f32_kernel": k 3, stride 1, cout in {32, 64} and the same alignment (a 128 x 64 tile).
+ *       "convnet3x3_f32_kernel": k 3, stride 1, cout >= 128 and the same alignment (the perceptual block's kernel).
+ *       "conv_f32_kernel" (the flow block's kernel): everything else, among it a k 1 conv with cin % 32 != 0.
+ *     residual may be out (each element is read, then written, by one thread).
+ *   avgpool_cl_f32: the 2 x 2, stride 2 average in the same summation order, ho = h / 2, wo = w / 2 (h, w >= 2).
+ *   clip_attnpool_f32: x [n][h][w] pixels of stride ldx, 2048 channels -> out [n][1024] fp32, CLIP's AttentionPool2d without the positional
+ *     embedding: tokens T = [mean over the h w positions; the positions], 32 heads of 64, only token 0 as the query.  wq, wk, wv [2048][2048]
+ *     and wc [1024][2048] are the projections' weights as torch holds them ([out][in]), bq, bk, bv [2048], bc [1024].  Evaluated in fp64 as
+ *     q = Wq T_0 + bq, s_t,h = (T_t . (Wk_h^T q_h) + q_h . bk_h) / 8, a = softmax over t, o_h = Wv_h (sum_t a_t,h T_t) + bv_h, out = Wc o + bc
+ *     (standard attention in another rounding order), rounded once to fp32.  Token sums go through slices of 256 tokens merged in order.
+ *     ws: dove_clip_attnpool_workspace_bytes (0 for an empty batch).
+ *   clipiqa_score: emb [n][dim] fp32, text [2 pairs][dim] fp64, already L2-normalised, rows (positive, negative) per pair.  In fp64:
+ *     f = emb / |emb|, l_j = logit_scale f . text_j, out[n] = mean over the pairs of 1 / (1 + exp(l_neg - l_pos)). */
+typedef struct dove_resnet_conv_f32_args {
+  unsigned int struct_size; /* = sizeof(dove_resnet_conv_f32_args) of the caller's header, as dove_conv_desc */
+  unsigned int reserved;    /* 0 */
+  const float* x;           /* [n][h][w_in] pixels of stride ldx, cin channels read */
+  const float* w;           /* [k][k][cin][cout] */
+  const float* bias;        /* [cout] or NULL */
+  const float* residual;    /* [n][ho][wo] pixels of stride ldr, cout channels, or NULL */
+  float* out;               /* [n][ho][wo] pixels of stride ldo, cout channels written */
+  int n, h, w_in, cin, cout, k, stride, pool;
+  int relu;
+  int reserved2;            /* 0 */
+  long long ldx, ldr, ldo;
+} dove_resnet_conv_f32_args;
+int dove_resnet_conv_f32(const dove_resnet_conv_f32_args* args, void* stream);
+const char* dove_resnet_conv_f32_kernel_name(const dove_resnet_conv_f32_args* args);
+int dove_avgpool_cl_f32(const float* x, long long ldx, int n, int h, int w, int c, float* out, long long ldo, void* stream);
+size_t dove_clip_attnpool_workspace_bytes(int n, int h, int w);
+int dove_clip_attnpool_f32(const float* x, long long ldx, int n, int h, int w, const float* wq, const float* bq, const float* wk,
+                           const float* bk, const float* wv, const float* bv, const float* wc, const float* bc, void* ws, size_t ws_bytes,
+                           float* out, void* stream);
+int dove_clipiqa_score(const float* emb, const double* text, int n, int pairs, int dim, double logit_scale, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
