@@ -140,12 +140,12 @@ def main(argv=None):
     ap.add_argument("--input_json", type=str, default=None, help="{clip name: prompt}; clips without an entry use the empty prompt (ref :590-594, :676)")
     ap.add_argument("--output_path", type=str, default="./results")
     ap.add_argument("--gt_dir", type=str, default=None, help="ground-truth folders / .npy / .y4m clips for --eval_metrics (ref :511)")
-    ap.add_argument("--eval_metrics", type=str, default="", help="any of 'psnr,ssim' (ref :513), on the GPU; with --metric_weights also 'lpips,lpips-vgg,dists' and the no-reference 'niqe' and 'clipiqa' (which need no --gt_dir); the other network metrics of pyiqa are not provided")
+    ap.add_argument("--eval_metrics", type=str, default="", help="any of 'psnr,ssim' (ref :513), on the GPU; with --metric_weights also 'lpips,lpips-vgg,dists' and the no-reference 'niqe', 'clipiqa' and 'musiq' (which need no --gt_dir); the other network metrics of pyiqa are not provided")
     ap.add_argument("--metric_weights", type=str, default="",
                     help="directory with the checkpoints of lpips / lpips-vgg / dists for --eval_metrics (alexnet*.pth, vgg16*.pth, "
                          "LPIPS_v0.1_alex*.pth, LPIPS_v0.1_vgg*.pth, DISTS_weights*.pth; dove_amd.percep) and the model of niqe "
                          "(niqe_modelparameters*.mat or niqe*.npz; dove_amd.niqe) and the files of clipiqa (RN50*.pt, clipiqa_text*.npz; "
-                         "dove_amd.clipiqa)")
+                         "dove_amd.clipiqa) and the checkpoint of musiq (musiq*.pth; dove_amd.musiq)")
     ap.add_argument("--png_save", action="store_true")
     ap.add_argument("--y4m_save", action="store_true",
                     help="write <clip>.y4m (YUV4MPEG2) with --fps and --save_format; with --chunk_len > 0 it is streamed chunk by chunk")
@@ -159,16 +159,21 @@ def main(argv=None):
     network = NETWORK_METRICS if args.metric_weights else ()
     no_ref = NR_METRICS if args.metric_weights else ()                    # no-reference: scored on the output alone
     if any(m not in FR_METRICS + network + no_ref for m in metrics):
-        known = "'psnr', 'ssim', 'lpips', 'lpips-vgg', 'dists', 'niqe' and 'clipiqa'" if network else "'psnr' and 'ssim'"
+        known = "'psnr', 'ssim', 'lpips', 'lpips-vgg', 'dists', 'niqe', 'clipiqa' and 'musiq'" if network else "'psnr' and 'ssim'"
         raise NotImplementedError(f"--eval_metrics {args.eval_metrics}: only {known} are computed here; " +
                                   ("the other pyiqa metrics are outside the path" if network else
                                    "the other pyiqa metrics need network weights and are outside the path "
-                                   "(--metric_weights DIR adds lpips, lpips-vgg, dists, niqe and clipiqa)"))
+                                   "(--metric_weights DIR adds lpips, lpips-vgg, dists, niqe and clipiqa, and musiq)"))
     if "clipiqa" in metrics:
         from . import clipiqa
         if clipiqa.find_file(args.metric_weights, "model") is None:      # as create_metric('clipiqa') without weights: not a metric here
             raise NotImplementedError(f"--eval_metrics clipiqa: {args.metric_weights} holds no {' / '.join(clipiqa.FILE_PATTERNS['model'])}; "
                                       "clipiqa is computed only from a CLIP RN50 checkpoint you supply (INTEGRATION.md 1j)")
+    if "musiq" in metrics:
+        from . import musiq
+        if musiq.find_file(args.metric_weights) is None:                 # as create_metric('musiq') without weights: not a metric here
+            raise NotImplementedError(f"--eval_metrics musiq: {args.metric_weights} holds no {musiq.FILE_PATTERN}; "
+                                      "musiq is computed only from a MUSIQ checkpoint you supply (INTEGRATION.md 1k)")
     if any(m not in no_ref for m in metrics) and not (args.gt_dir or args.eval_psnr_dir):
         raise ValueError(f"--eval_metrics {args.eval_metrics} needs --gt_dir")
     # with --eval_psnr_dir, PSNR stays on that flag's CPU path (against its folders, as before); the rest runs on the GPU against

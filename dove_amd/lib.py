@@ -60,6 +60,11 @@ class ImageView(C.Structure):
                 ("sn", C.c_longlong), ("sc", C.c_longlong), ("sh", C.c_longlong), ("sw", C.c_longlong)]
 
 
+class MusiqScale(C.Structure):
+    """dove_musiq_scale (include/dove_hip.h): one scale's image size, leading zero padding and whether it is resized."""
+    _fields_ = [(n, C.c_int) for n in ("rh", "rw", "pad_top", "pad_left", "resized", "reserved")]
+
+
 class YuvFormat(C.Structure):
     """dove_yuv_format (include/dove_hip.h): a fixed-point 3x3 matrix (rint(c * 65536)), the offsets, the chroma layout and siting."""
     _fields_ = [("coef", C.c_int * 9), ("offset", C.c_int * 3), ("chroma", C.c_int), ("siting_h", C.c_int)]
@@ -254,6 +259,14 @@ SIGNATURES = {
     "dove_avgpool_cl_f32": [_VP, _LL, _I, _I, _I, _I, _VP, _LL, _VP],
     "dove_clip_attnpool_f32": [_VP, _LL, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP, _VP],
     "dove_clipiqa_score": [_VP, _VP, _I, _I, _I, C.c_double, _VP, _VP],
+    # MUSIQ (csrc/musiq.hip): the patch gather, GroupNorm, LayerNorm, embeddings, fp32 attention, GELU and the fp64 head
+    "dove_musiq_patches_f32": [C.POINTER(ImageView), _I, _I, _I, _I, C.POINTER(MusiqScale), _VP, _I, _I, _I, _VP, _VP],
+    "dove_musiq_groupnorm_f32": [_VP, _VP, _VP, _VP, _VP, _VP, _LL, _I, _I, C.c_double, _I, _I, _VP, _VP],
+    "dove_layernorm_f32": [_VP, _LL, _LL, _I, _VP, _VP, C.c_double, _VP, _LL, _VP],
+    "dove_musiq_embed_f32": [_VP, _VP, _VP, _VP, _VP, _I, _I, _I, _VP, _VP],
+    "dove_mha_f32": [_VP, _VP, _VP, _LL, _I, _I, _I, _F, _VP, _LL, _VP],
+    "dove_gelu_f32": [_VP, _LL, _VP, _VP],
+    "dove_musiq_score": [_VP, _LL, _VP, _VP, _I, _I, _I, _VP, _VP],
 }
 PLAIN = {"dove_last_error": (C.c_char_p, []), "dove_abi_version": (C.c_int, []), "dove_comm_destroy": (None, [C.c_void_p]),
          "dove_conv_gn_partial_rows": (C.c_longlong, [C.POINTER(ConvDesc)]),
@@ -284,7 +297,8 @@ PLAIN = {"dove_last_error": (C.c_char_p, []), "dove_abi_version": (C.c_int, []),
          "dove_dists_layer_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I]),
          "dove_niqe_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
          "dove_resnet_conv_f32_kernel_name": (C.c_char_p, [C.POINTER(ResnetConvF32Args)]),
-         "dove_clip_attnpool_workspace_bytes": (C.c_size_t, [_I, _I, _I])}
+         "dove_clip_attnpool_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
+         "dove_mha_f32_tiles": (None, [C.POINTER(C.c_int), C.POINTER(C.c_int)])}
 
 
 def kernel_source_sha256() -> str:

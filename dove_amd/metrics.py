@@ -5,8 +5,9 @@ Three surfaces:
   - ``create_metric(name)``: pyiqa's ``create_metric`` surface for 'psnr' and 'ssim', so the reference's metric code runs with
     ``import dove_amd.metrics as pyiqa``; ``create_metric(name, weights=W)`` gives 'lpips', 'lpips-vgg' and 'dists' from user-supplied
     checkpoints (dove_amd.percep) and the no-reference 'niqe' from a user-supplied pristine model (dove_amd.niqe.NiqeModel) and 'clipiqa'
-    from a user-supplied CLIP RN50 checkpoint (dove_amd.clipiqa.ClipIqaWeights), both called as ``metric(pred)``; any other name, or one
-    of these without weights, raises ``NotImplementedError``;
+    from a user-supplied CLIP RN50 checkpoint (dove_amd.clipiqa.ClipIqaWeights) and 'musiq' from a user-supplied MUSIQ checkpoint
+    (dove_amd.musiq.MusiqWeights), all called as ``metric(pred)``; any other name, or one of these without weights, raises
+    ``NotImplementedError``;
   - ``clip_metrics(pred_u8, gt_u8, names, crop, test_y_channel, is_center)``: the per-clip logic of eval_metrics.py (match_resolution,
     crop_border, rgb_to_y, mean over frames), as views on the device; ``nr_clip_metrics(pred_u8, names, weights)`` is its ground-truth-free
     half (the no-reference metrics on the predictions as they are).
@@ -25,7 +26,7 @@ from . import ops
 
 FR_METRICS = ("psnr", "ssim")
 NETWORK_METRICS = ("lpips", "lpips-vgg", "dists")       # computed by dove_amd.percep when the caller passes weights
-NR_METRICS = ("niqe", "clipiqa")                        # no-reference: dove_amd.niqe (a NiqeModel) and dove_amd.clipiqa (ClipIqaWeights)
+NR_METRICS = ("niqe", "clipiqa", "musiq")               # no-reference: dove_amd.niqe (NiqeModel), .clipiqa (ClipIqaWeights), .musiq (MusiqWeights)
 
 
 def _unsupported(name: str) -> NotImplementedError:
@@ -93,7 +94,7 @@ def create_metric(name: str, weights=None, **kwargs):
     """``pyiqa.create_metric`` for the full-reference metrics computed here: 'psnr' and 'ssim' with pyiqa's default options, and, given
     ``weights`` (percep.LpipsWeights / percep.DistsWeights), 'lpips', 'lpips-vgg' and 'dists' (lower is better, [N] fp64); with
     ``weights`` a niqe.NiqeModel, the no-reference 'niqe' (``metric(pred)``, lower is better, [N] fp64); with clipiqa.ClipIqaWeights, the
-    no-reference 'clipiqa' (``metric(pred)``, higher is better, [N] fp64)."""
+    no-reference 'clipiqa', and with musiq.MusiqWeights the no-reference 'musiq' (``metric(pred)``, higher is better, [N] fp64)."""
     key = name.strip().lower()
     if weights is not None:
         if key not in NETWORK_METRICS + NR_METRICS:
@@ -103,6 +104,9 @@ def create_metric(name: str, weights=None, **kwargs):
         if key == "clipiqa":
             from . import clipiqa
             return clipiqa.ClipIqaMetric(weights)
+        if key == "musiq":
+            from . import musiq
+            return musiq.MusiqMetric(weights)
         if key in NR_METRICS:
             from . import niqe
             return niqe.NiqeMetric(weights)
@@ -167,7 +171,7 @@ def rgb_to_y(frames: torch.Tensor) -> torch.Tensor:
 def clip_metrics(pred_u8: torch.Tensor, gt_u8: torch.Tensor, names, crop: int = 0, test_y_channel: bool = False,
                  is_center: bool = False, name: str | None = None, weights: dict | None = None) -> dict:
     """Per-clip metrics as eval_metrics.py computes them -> {metric: mean over frames of the per-frame value}: the full-reference ones,
-    and 'niqe' / 'clipiqa' (given their weights in ``weights``) on the uncropped predictions (``crop`` and ``test_y_channel`` do not apply to them).
+    and 'niqe' / 'clipiqa' / 'musiq' (given their weights in ``weights``) on the uncropped predictions (``crop`` and ``test_y_channel`` do not apply to them).
 
     ``pred_u8`` / ``gt_u8``: [F,H,W,3] uint8 frames (a host tensor is uploaded as uint8).  Steps of the reference: match_resolution
     (common frame count, top-left or centre crop to the common H x W), crop_border, optional rgb_to_y; all of them are views."""

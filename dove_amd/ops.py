@@ -1336,3 +1336,170 @@ def clipiqa_score(emb: torch.Tensor, text: torch.Tensor, logit_scale: float) -> 
     L.check(L.load().dove_clipiqa_score(L.ptr(emb), L.ptr(text), emb.shape[0], text.shape[0] // 2, emb.shape[1], float(logit_scale), L.ptr(out),
                                         L.stream_ptr()), "dove_clipiqa_score")
     return out
+
+
+# ---- MUSIQ (csrc/musiq.hip): the patch gather, per-patch GroupNorm, LayerNorm, embeddings, fp32 attention, GELU and the fp64 head --------
+def linear_f32(x: torch.Tensor, w: torch.Tensor, bias=None, *, residual: torch.Tensor | None = None, relu: bool = False,
+               out: torch.Tensor | None = None) -> torch.Tensor:
+    """x float32 [M,K] rows (a column slice is fine), w float32 [1,1,K,N] (the Linear's weight transposed) -> [M,N] = relu?((x w + bias) +
+    residual) on the 1 x 1 walk of ``resnet_conv_f32`` with the rows as pixels (K % 32 == 0, N % 4 == 0): one fp32 FMA chain in K order
+    per output.  ``residual`` and ``out`` may be one tensor."""
+    if x.dim() != 2 or (residual is not None and residual.dim() != 2) or (out is not None and out.dim() != 2):
+        raise ValueError(f"linear_f32: x {tuple(x.shape)}, residual and out must be [M,K] / [M,N] matrices")
+    as4 = lambda t: None if t is None else t.unsqueeze(0).unsqueeze(0)
+    return resnet_conv_f32(as4(x), w, bias, residual=as4(residual), relu=relu, out=as4(out))[0, 0]
+
+
+def _strided_on_device(what: str, *tensors) -> None:
+    """``require_cuda`` for operands that may be strided views: on the current HIP device, no word about contiguity."""
+    for t in tensors:
+        if not t.is_cuda or t.device.index != torch.cuda.current_device():
+            raise RuntimeError(f"{what}: tensors must be on the current HIP device (`cuda:{torch.cuda.current_device()}`), got {t.device}")
+
+
+def musiq_scales(scales) -> "C.Array":
+    """Three (rh, rw, pad_top, pad_left, resized) tuples -> the dove_musiq_scale[3] of ``musiq_patches_f32``."""
+    arr = (L.MusiqScale * 3)()
+    for a, (rh, rw, pt, pl, resized) in zip(arr, scales):
+        a.rh, a.rw, a.pad_top, a.pad_left, a.resized = int(rh), int(rw), int(pt), int(pl), int(bool(resized))
+    return arr
+
+
+def musiq_patches_f32(img: torch.Tensor, scales, tokens: torch.Tensor, before: int = 0, side: int = 32) -> torch.Tensor:
+    """img: an [N,1|3,H,W] view (uint8 read as u / 255, float32 or bfloat16 in [0,1]; any strides, no copy), ``scales`` three (rh, rw,
+    pad_top, pad_left, resized), ``tokens`` int32 [T,4] on the device (scale, patch row, patch column, spatial index) -> float32
+    [N T,side,side,3]: every token's 32 x 32 patch of 2 v - 1 at [before, before + 32) of its frame, 0 around it (before 2, side 37: the
+    frame of the stem's 7 x 7 stride-2 conv).  Resized scales are bicubic in fp64, rounded once (csrc/musiq.hip)."""
+    if img.dim() != 4 or img.shape[1] not in (1, 3) or not img.is_cuda:
+        raise ValueError(f"musiq_patches_f32: need an [N,1|3,H,W] view on the HIP device, got {tuple(img.shape)} on {img.device}")
+    _strided_on_device("musiq_patches_f32", img)
+    L.require_cuda(tokens)
+    if tokens.dtype != torch.int32 or tokens.dim() != 2 or tokens.shape[1] != 4 or not tokens.is_contiguous() or len(scales) != 3:
+        raise ValueError("musiq_patches_f32: tokens must be contiguous int32 [T,4] and scales three tuples")
+    N, Cc, H, W = img.shape
+    T = tokens.shape[0]
+    out = torch.empty(N * T, side, side, 3, dtype=torch.float32, device=img.device)
+    if N * T == 0:
+        return out
+    v = _image_view(img)
+    L.check(L.load().dove_musiq_patches_f32(C.byref(v), N, Cc, H, W, musiq_scales(scales), L.ptr(tokens), T, before, side, L.ptr(out),
+                                            L.stream_ptr()), "dove_musiq_patches_f32")
+    return out
+
+
+def musiq_groupnorm_f32(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, *, relu: bool = False, pool: bool = False,
+                        y: torch.Tensor | None = None, gamma_y=None, beta_y=None, out: torch.Tensor | None = None) -> torch.Tensor:
+    """GroupNorm(32 groups) of every map of contiguous float32 [P,S,S,C] with fp64 two-pass statistics and one rounding; ``y``: the sum with
+    the GroupNorm of a second operand of the same shape; ``relu``; ``pool``: the zero-'same' (0 before, 1 after) 3 x 3 stride-2 max pool of
+    the result -> [P,S/2,S/2,C].  ``out`` may be ``x`` without the pool."""
+    L.require_cuda(x, gamma, beta, y, gamma_y, beta_y)
+    if x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != x.shape[2] or not x.is_contiguous():
+        raise ValueError(f"musiq_groupnorm_f32: x {tuple(x.shape)} {x.dtype} must be contiguous float32 [P,S,S,C]")
+    P, S, _, Cc = x.shape
+    vecs = [gamma, beta] + ([gamma_y, beta_y] if y is not None else [])
+    if any(t is None or t.dtype != torch.float32 or t.numel() != Cc or not t.is_contiguous() for t in vecs):
+        raise ValueError(f"musiq_groupnorm_f32: gamma and beta (of both operands) must be float32 [{Cc}]")
+    if y is not None and (y.shape != x.shape or y.dtype != torch.float32 or not y.is_contiguous()):
+        raise ValueError(f"musiq_groupnorm_f32: y must be contiguous float32 {tuple(x.shape)}")
+    shape = (P, S // 2, S // 2, Cc) if pool else (P, S, S, Cc)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError(f"musiq_groupnorm_f32: out must be contiguous float32 {shape}")
+    if P == 0:
+        return out
+    L.check(L.load().dove_musiq_groupnorm_f32(L.ptr(x), L.ptr(gamma), L.ptr(beta), L.ptr(y), L.ptr(gamma_y if y is not None else None),
+                                              L.ptr(beta_y if y is not None else None), P, S, Cc, float(eps), int(bool(relu)), int(bool(pool)),
+                                              L.ptr(out), L.stream_ptr()), "dove_musiq_groupnorm_f32")
+    return out
+
+
+def layernorm_f32(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, out: torch.Tensor | None = None) -> torch.Tensor:
+    """LayerNorm over the last axis of float32 [R,D] rows (any row stride) with fp64 two-pass statistics and one rounding."""
+    _strided_on_device("layernorm_f32", x)
+    L.require_cuda(gamma, beta)
+    if x.dtype != torch.float32 or x.dim() != 2 or (x.shape[1] > 1 and x.stride(1) != 1) or x.stride(0) < x.shape[1]:
+        raise ValueError(f"layernorm_f32: x {tuple(x.shape)} {x.dtype} with strides {x.stride()} must be float32 [R,D] rows")
+    R, D = x.shape
+    if any(t.dtype != torch.float32 or t.numel() != D or not t.is_contiguous() for t in (gamma, beta)):
+        raise ValueError(f"layernorm_f32: gamma and beta must be float32 [{D}]")
+    if out is None:
+        out = torch.empty(R, D, dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != (R, D) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError(f"layernorm_f32: out must be contiguous float32 {(R, D)}")
+    if R == 0:
+        return out
+    L.check(L.load().dove_layernorm_f32(L.ptr(x), x.stride(0), R, D, L.ptr(gamma), L.ptr(beta), float(eps), L.ptr(out), D, L.stream_ptr()),
+            "dove_layernorm_f32")
+    return out
+
+
+def musiq_embed_f32(emb: torch.Tensor, pos: torch.Tensor, scale_emb: torch.Tensor, cls: torch.Tensor, tokens: torch.Tensor) -> torch.Tensor:
+    """emb float32 [N T,D] patch embeddings, pos [100,D], scale_emb [3,D], cls [D], tokens int32 [T,4] -> float32 [N,T + 1,D]: the cls token,
+    then (emb + pos[spatial index]) + scale_emb[scale] per token."""
+    L.require_cuda(emb, pos, scale_emb, cls, tokens)
+    T, D = tokens.shape[0], emb.shape[1]
+    if any(t.dtype != torch.float32 or not t.is_contiguous() for t in (emb, pos, scale_emb, cls)) or emb.dim() != 2 or T == 0 or \
+            emb.shape[0] % T or pos.shape[-1] != D or scale_emb.shape[-1] != D or cls.numel() != D or tokens.dtype != torch.int32:
+        raise ValueError(f"musiq_embed_f32: emb {tuple(emb.shape)} must be contiguous float32 [N T,D] with T = {T} and the tables D wide")
+    N = emb.shape[0] // T
+    out = torch.empty(N, T + 1, D, dtype=torch.float32, device=emb.device)
+    if N == 0:
+        return out
+    L.check(L.load().dove_musiq_embed_f32(L.ptr(emb), L.ptr(pos), L.ptr(scale_emb), L.ptr(cls), L.ptr(tokens), N, T, D, L.ptr(out), L.stream_ptr()),
+            "dove_musiq_embed_f32")
+    return out
+
+
+def mha_f32_tiles() -> tuple:
+    """(Q tile, KV tile) of ``mha_f32``'s kernel; needs no device."""
+    q, kv = C.c_int(0), C.c_int(0)
+    L.load().dove_mha_f32_tiles(C.byref(q), C.byref(kv))
+    return q.value, kv.value
+
+
+def mha_f32(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float | None = None) -> torch.Tensor:
+    """q, k, v float32 [N,T,heads * 64] (column slices of one QKV buffer are fine) -> softmax(scale q k^T) v per frame and head, float32
+    [N,T,heads * 64]; flash-style fp32 MFMA attention (csrc/musiq.hip).  ``scale`` defaults to 1 / 8."""
+    _strided_on_device("mha_f32", q, k, v)
+    N, T, D = q.shape
+    ok = lambda t: t.dtype == torch.float32 and tuple(t.shape) == (N, T, D) and t.stride(2) == 1 and t.stride(1) == q.stride(1) and \
+        (N == 1 or t.stride(0) == T * t.stride(1))
+    if D % 64 or not (ok(q) and ok(k) and ok(v)):
+        raise ValueError(f"mha_f32: q, k, v must be float32 [N,T,64 heads] rows of one stride, got {tuple(q.shape)} {tuple(k.shape)} {tuple(v.shape)}")
+    out = torch.empty(N, T, D, dtype=torch.float32, device=q.device)
+    if N * T == 0:
+        return out
+    L.check(L.load().dove_mha_f32(L.ptr(q), L.ptr(k), L.ptr(v), q.stride(1), N, T, D // 64, 0.125 if scale is None else float(scale), L.ptr(out), D,
+                                  L.stream_ptr()), "dove_mha_f32")
+    return out
+
+
+def gelu_f32(x: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Exact-erf GELU of a contiguous float32 tensor in fp32: 0.5 x (1 + erff(x / sqrt 2)).  ``out`` may be ``x``."""
+    L.require_cuda(x)
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError(f"gelu_f32: x {tuple(x.shape)} {x.dtype} must be contiguous float32")
+    if out is None:
+        out = torch.empty_like(x)
+    elif out.shape != x.shape or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("gelu_f32: out must be contiguous float32 of x's shape")
+    if x.numel():
+        L.check(L.load().dove_gelu_f32(L.ptr(x), x.numel(), L.ptr(out), L.stream_ptr()), "dove_gelu_f32")
+    return out
+
+
+def musiq_score(features: torch.Tensor, w: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """features float32 [N,D] (any row stride), head weight float32 [K,D] and bias [K] -> float64 [N]: the head in fp64; K = 1 gives the
+    row, K > 1 the mean of softmax(row) over the ratings 1 .. K."""
+    _strided_on_device("musiq_score", features)
+    L.require_cuda(w, b)
+    N, D = features.shape
+    if features.dtype != torch.float32 or (D > 1 and features.stride(1) != 1) or w.dtype != torch.float32 or w.dim() != 2 or w.shape[1] != D or \
+            not w.is_contiguous() or b.dtype != torch.float32 or b.numel() != w.shape[0]:
+        raise ValueError(f"musiq_score: features {tuple(features.shape)} must be float32 [N,D] rows, w float32 [K,D], b float32 [K]")
+    out = torch.empty(N, dtype=torch.float64, device=features.device)
+    if N:
+        L.check(L.load().dove_musiq_score(L.ptr(features), features.stride(0), L.ptr(w), L.ptr(b), N, D, w.shape[0], L.ptr(out), L.stream_ptr()),
+                "dove_musiq_score")
+    return out

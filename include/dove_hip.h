@@ -841,6 +841,51 @@ int dove_clip_attnpool_f32(const float* x, long long ldx, int n, int h, int w, c
                            float* out, void* stream);
 int dove_clipiqa_score(const float* emb, const double* text, int n, int pairs, int dim, double logit_scale, double* out, void* stream);
 
+/* MUSIQ (csrc/musiq.hip): what pyiqa's `musiq` needs beside the convs and GEMMs above (its 1 x 1 convs and Linears run on
+ * dove_resnet_conv_f32 with tokens as pixels, its 3 x 3 conv too, its 7 x 7 stem conv on dove_convnet_conv_f32 with pad 0 over the 37 x 37 frame
+ * that the gather writes).  Channels-last fp32, no atomics, identical bits on repetition, a frame's result independent of the batch.  None of
+ * these needs a workspace.
+ *   musiq_patches_f32: img is n frames [c][h][w] (c in {1, 3}; one channel is repeated; f32 / bf16 in [0,1] or u8 read as u / 255.0 in fp64, any
+ *     strides) -> out [n tokens_per_frame][side][side][3].  tokens [tokens_per_frame][4] int32 on the device: (scale 0..2, patch row, patch
+ *     column, spatial index); scales[3] on the host.  Token t's 32 x 32 patch lies at [before, before + 32)^2 of its side x side frame, 0
+ *     around it.  Patch pixel (py, px) is pixel (32 row + py - pad_top, 32 column + px - pad_left) of the scale's rh x rw image and 0 outside
+ *     it.  With v' = 2 v - 1: a scale with resized == 0 (rh == h, rw == w) gives (float)v'; a resized scale gives torch's bicubic of v'
+ *     (A = -0.75, align_corners = False, source coordinate (h / rh) (y + 0.5) - 0.5, taps clamped at the border, no antialias), evaluated in
+ *     fp64 from the source values, rows first, taps ascending, and rounded once to fp32.
+ *   musiq_groupnorm_f32: x [maps][side][side][c] dense, 32 groups of c / 32 channels, statistics per map and group in fp64 in two passes (mean,
+ *     then squared deviations; eight threads per group in a fixed order), biased variance.  out = relu?((x - mean) rstd gamma + beta [+ the same
+ *     of y with gamma_y, beta_y]), the bracket evaluated in fp64 and rounded once.  pool != 0 (one operand only): out is [maps][side / 2]
+ *     [side / 2][c], the 3 x 3 stride-2 max over those values with zero padding 0 before and 1 after.  out may be x when pool == 0.
+ *   layernorm_f32: rows of dim values at stride ldx -> stride ldo: fp64 mean and biased variance in two passes, fixed order, one rounding.
+ *   musiq_embed_f32: out [n][tokens_per_frame + 1][dim]: row 0 = cls, row 1 + t = (emb[f tokens_per_frame + t] + pos[spatial(t)]) +
+ *     scale_emb[scale(t)], fp32.
+ *   mha_f32: q, k, v: rows of stride ld, n frames of t rows each, head h in columns [64 h, 64 h + 64) (they may be slices of one QKV buffer);
+ *     out the same with stride ldo.  softmax(scale q k^T) v per frame and head in fp32 on v_mfma_f32_32x32x2_f32, flash-style: Q tiles of 64
+ *     rows, KV tiles of 32 keys (dove_mha_f32_tiles reports them), a running row maximum, row sums in a fixed order, accurate expf; no t x t
+ *     matrix is stored.  Any t >= 1; ld, ldo multiples of 4 and 16-byte aligned pointers.
+ *   gelu_f32: out = 0.5 x (1 + erff(x / sqrt 2)) in fp32, its own pass; out may be x.
+ *   musiq_score: features n rows of dim at stride ld (the normalised token 0), w [k][dim], b [k] fp32 -> out[n] fp64: row = w f + b in fp64;
+ *     k == 1: the row; k > 1 (the AVA head): sum_j (j + 1) softmax(row)_j.  k <= 64. */
+typedef struct dove_musiq_scale {
+  int rh, rw;            /* the scale's image */
+  int pad_top, pad_left; /* zero padding in front of it: (32 ceil(rh / 32) - rh) / 2, likewise for rw */
+  int resized;           /* 0: the original resolution, read as it is */
+  int reserved;          /* 0 */
+} dove_musiq_scale;
+int dove_musiq_patches_f32(const dove_image_view* img, int n, int c, int h, int w, const dove_musiq_scale* scales, const int* tokens,
+                           int tokens_per_frame, int before, int side, float* out, void* stream);
+int dove_musiq_groupnorm_f32(const float* x, const float* gamma, const float* beta, const float* y, const float* gamma_y, const float* beta_y,
+                             long long maps, int side, int c, double eps, int relu, int pool, float* out, void* stream);
+int dove_layernorm_f32(const float* x, long long ldx, long long rows, int dim, const float* gamma, const float* beta, double eps, float* out,
+                       long long ldo, void* stream);
+int dove_musiq_embed_f32(const float* emb, const float* pos, const float* scale_emb, const float* cls, const int* tokens, int n,
+                         int tokens_per_frame, int dim, float* out, void* stream);
+int dove_mha_f32(const float* q, const float* k, const float* v, long long ld, int n, int t, int heads, float scale, float* out, long long ldo,
+                 void* stream);
+void dove_mha_f32_tiles(int* q_tile, int* kv_tile);
+int dove_gelu_f32(const float* x, long long count, float* out, void* stream);
+int dove_musiq_score(const float* features, long long ld, const float* w, const float* b, int n, int dim, int k, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
