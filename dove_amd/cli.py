@@ -6,10 +6,10 @@ Every flag of the reference's parser (ref :507-554) is accepted: ``--input_dir -
 ``finetune/scripts/color_fix_util.py`` on the GPU, dove_amd.colorfix) fixes every output frame against the clip's upscaled input.  ``--fps`` / ``--save_format`` describe the mp4
 container the reference writes with imageio - frame files carry neither, so they are accepted and reported (with ``--y4m_save`` they are the
 frame rate and chroma layout of the ``<clip>.y4m`` written: YUV4MPEG2, dove_amd.y4m / dove_amd.stream); ``--is_cpu_offload``
-calls ``pipe.enable_sequential_cpu_offload()`` like the reference (a no-op with 288 GB of HBM); ``--eval_metrics`` knows ``psnr`` and
-``ssim``, computed on the GPU (dove_amd.metrics) from the uint8 frames written to disk against ``--gt_dir/<clip>``, as the reference's
+calls ``pipe.enable_sequential_cpu_offload()`` like the reference (a no-op with 288 GB of HBM); ``--eval_metrics`` knows the metrics of
+``dove_amd.metrics.REGISTRY``, computed on the GPU from the uint8 frames written to disk against ``--gt_dir/<clip>``, as the reference's
 ``eval_metrics.py`` scores the saved files; the per-clip values go to ``metrics_<names>.json`` in ``--output_path`` (the reference's
-structure, ref :755-776); ``--metric_weights DIR`` adds ``lpips``, ``lpips-vgg`` and ``dists`` from checkpoints in that directory (dove_amd.percep); without it they, and always the other network metrics of pyiqa (clipiqa, ...), are refused; ``--dtype`` other than bfloat16 is refused.  Inputs are PNG folders,
+structure, ref :755-776); the registry's metrics that need weights take them from ``--metric_weights DIR`` (``--help`` lists the files); without it they, and always the other metrics of pyiqa, are refused; ``--dtype`` other than bfloat16 is refused.  Inputs are PNG folders,
 ``.npy`` clips (uint8 [F,H,W,3]) or ``.y4m`` files because H.264 decoding (decord) is outside the accelerated path; outputs are PNG
 folders, ``.npy`` or ``.y4m`` (``--y4m_save``; streamed chunk by chunk when ``--chunk_len > 0``).  ``--random_init`` builds the CogVideoX1.5-5B architecture with synthetic weights (no checkpoint is
 available offline).  ``--eval_psnr_dir`` computes plain PSNR (10*log10(1/MSE), per-frame mean) on the CPU against ground-truth folders; with it,
@@ -58,6 +58,27 @@ def check_dtype(args):
     if args.dtype != "bfloat16":
         raise ValueError(f"--dtype {args.dtype}: the HIP path computes in bfloat16 (the reference's default, ref :525); float16 / float32 "
                          "are not implemented (INTEGRATION.md, 'dtype')")
+
+
+def check_eval_metrics(metrics, metric_weights: str, has_gt: bool) -> None:
+    """Refuse what ``--eval_metrics`` cannot be computed from, before a model is built: a name outside ``metrics.REGISTRY``, a metric that
+    needs weights without ``--metric_weights`` or without its main file there, a full-reference metric without ground truth."""
+    from .metrics import FR, NETWORK, NR, REGISTRY, metric_names, name_list
+    weighted = metric_names(NETWORK, NR)
+    known = metric_names(FR) + (weighted if metric_weights else ())
+    flag = ",".join(metrics)
+    if any(m not in known for m in metrics):
+        raise NotImplementedError(f"--eval_metrics {flag}: only {name_list(repr(m) for m in known)} are computed here; " +
+                                  ("the other pyiqa metrics are outside the path" if metric_weights else
+                                   "the other pyiqa metrics need network weights and are outside the path "
+                                   f"(--metric_weights DIR adds {name_list(weighted)})"))
+    for m in metrics:
+        spec = REGISTRY[m]
+        if spec.probe is not None and not spec.probe(metric_weights):   # as create_metric(m) without weights: not a metric here
+            raise NotImplementedError(f"--eval_metrics {m}: {metric_weights} holds none of the files of {m} ({', '.join(spec.patterns)}); "
+                                      f"{m} is computed only from files you supply (INTEGRATION.md {spec.section})")
+    if any(m not in metric_names(NR) for m in metrics) and not has_gt:
+        raise ValueError(f"--eval_metrics {flag} needs --gt_dir")
 
 
 def build_pipe(args):
@@ -135,17 +156,18 @@ def _save_clip_y4m(out, video, pads, args, path, chroma, color_fix, need_frames)
 
 
 def main(argv=None):
+    from . import eval_metrics
+    from . import metrics as M
     ap = argparse.ArgumentParser(description="VSR using DOVE on MI355X (dove_amd)")
     ap.add_argument("--input_dir", type=str, required=True)
     ap.add_argument("--input_json", type=str, default=None, help="{clip name: prompt}; clips without an entry use the empty prompt (ref :590-594, :676)")
     ap.add_argument("--output_path", type=str, default="./results")
     ap.add_argument("--gt_dir", type=str, default=None, help="ground-truth folders / .npy / .y4m clips for --eval_metrics (ref :511)")
-    ap.add_argument("--eval_metrics", type=str, default="", help="any of 'psnr,ssim' (ref :513), on the GPU; with --metric_weights also 'lpips,lpips-vgg,dists' and the no-reference 'niqe', 'clipiqa' and 'musiq' (which need no --gt_dir); the other network metrics of pyiqa are not provided")
-    ap.add_argument("--metric_weights", type=str, default="",
-                    help="directory with the checkpoints of lpips / lpips-vgg / dists for --eval_metrics (alexnet*.pth, vgg16*.pth, "
-                         "LPIPS_v0.1_alex*.pth, LPIPS_v0.1_vgg*.pth, DISTS_weights*.pth; dove_amd.percep) and the model of niqe "
-                         "(niqe_modelparameters*.mat or niqe*.npz; dove_amd.niqe) and the files of clipiqa (RN50*.pt, clipiqa_text*.npz; "
-                         "dove_amd.clipiqa) and the checkpoint of musiq (musiq*.pth; dove_amd.musiq)")
+    ap.add_argument("--eval_metrics", type=str, default="",
+                    help=f"any of '{','.join(M.metric_names(M.FR))}' (ref :513), on the GPU; with --metric_weights also "
+                         f"'{','.join(M.metric_names(M.NETWORK))}' and the no-reference '{','.join(M.metric_names(M.NR))}' (which need no "
+                         "--gt_dir); the other network metrics of pyiqa are not provided")
+    ap.add_argument("--metric_weights", type=str, default="", help=f"directory with the files of {M.weights_help()}")
     ap.add_argument("--png_save", action="store_true")
     ap.add_argument("--y4m_save", action="store_true",
                     help="write <clip>.y4m (YUV4MPEG2) with --fps and --save_format; with --chunk_len > 0 it is streamed chunk by chunk")
@@ -154,28 +176,7 @@ def main(argv=None):
     args = ap.parse_args(argv)
     check_dtype(args)
     metrics = [m.strip().lower() for m in args.eval_metrics.split(",") if m.strip()]
-    from . import eval_metrics
-    from .metrics import FR_METRICS, NETWORK_METRICS, NR_METRICS
-    network = NETWORK_METRICS if args.metric_weights else ()
-    no_ref = NR_METRICS if args.metric_weights else ()                    # no-reference: scored on the output alone
-    if any(m not in FR_METRICS + network + no_ref for m in metrics):
-        known = "'psnr', 'ssim', 'lpips', 'lpips-vgg', 'dists', 'niqe', 'clipiqa' and 'musiq'" if network else "'psnr' and 'ssim'"
-        raise NotImplementedError(f"--eval_metrics {args.eval_metrics}: only {known} are computed here; " +
-                                  ("the other pyiqa metrics are outside the path" if network else
-                                   "the other pyiqa metrics need network weights and are outside the path "
-                                   "(--metric_weights DIR adds lpips, lpips-vgg, dists, niqe and clipiqa, and musiq)"))
-    if "clipiqa" in metrics:
-        from . import clipiqa
-        if clipiqa.find_file(args.metric_weights, "model") is None:      # as create_metric('clipiqa') without weights: not a metric here
-            raise NotImplementedError(f"--eval_metrics clipiqa: {args.metric_weights} holds no {' / '.join(clipiqa.FILE_PATTERNS['model'])}; "
-                                      "clipiqa is computed only from a CLIP RN50 checkpoint you supply (INTEGRATION.md 1j)")
-    if "musiq" in metrics:
-        from . import musiq
-        if musiq.find_file(args.metric_weights) is None:                 # as create_metric('musiq') without weights: not a metric here
-            raise NotImplementedError(f"--eval_metrics musiq: {args.metric_weights} holds no {musiq.FILE_PATTERN}; "
-                                      "musiq is computed only from a MUSIQ checkpoint you supply (INTEGRATION.md 1k)")
-    if any(m not in no_ref for m in metrics) and not (args.gt_dir or args.eval_psnr_dir):
-        raise ValueError(f"--eval_metrics {args.eval_metrics} needs --gt_dir")
+    check_eval_metrics(metrics, args.metric_weights, bool(args.gt_dir or args.eval_psnr_dir))
     # with --eval_psnr_dir, PSNR stays on that flag's CPU path (against its folders, as before); the rest runs on the GPU against
     # --gt_dir (or the --eval_psnr_dir folders when --gt_dir is not given)
     gpu_metrics = [m for m in metrics if not (m == "psnr" and args.eval_psnr_dir)]

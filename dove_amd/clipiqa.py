@@ -21,7 +21,7 @@ in fp64 and rounded once to fp32.  Frames go through the tower in groups sized s
 from __future__ import annotations
 
 import argparse
-import glob
+import functools
 import gzip
 import math
 import os
@@ -32,9 +32,9 @@ from dataclasses import dataclass, field
 import numpy as np
 import torch
 
-from . import ops
+from . import iqa, ops
 from .flow import pack_conv_weight
-from .metrics import _as_nchw
+from .iqa import ACTIVATION_BUDGET, FLOAT32_DTYPES, GpuMetric, find_file, find_first, for_groups, score_folder
 from .percep import _checked, _strip, _Weights
 
 CLIP_MEAN, CLIP_STD = (0.48145466, 0.4578275, 0.40821073), (0.26862954, 0.26130258, 0.27577711)
@@ -52,7 +52,6 @@ TEXT_WIDTH, TEXT_HEADS, TEXT_LAYERS, VOCAB = 512, 8, 12, 49408
 # of conv1 and conv2 at 1/4 side, (256 + 128 + 128) / 16 = 32 floats per input pixel.  The stem's conv3 (32 in, 64 out at 1/2 side) and
 # stage 1's first block (64 + 64 next to the 256-channel identity, which conv3 overwrites in place) need 24.  Measured with
 # tools/clipiqa_bench.py (docs/kernels.md).  One 2880 x 5120 frame is 1.9 GB, so 4 GiB holds two of them and 36 frames of 720 x 1280.
-ACTIVATION_BUDGET = 4 << 30
 FILE_PATTERNS = {"model": ("RN50*.pt", "RN50*.pth"), "text": ("clipiqa_text*.npz",), "vocab": ("bpe_simple_vocab_16e6.txt*",)}
 TEXT_DRAW = 50                                      # random_clipiqa_state's text features: see there
 COUNTERS = {"groups": 0}                            # tower groups walked, for tests and tools
@@ -167,24 +166,8 @@ def _normalised(features) -> torch.Tensor:
     return (t / t.norm(dim=1, keepdim=True)).contiguous()
 
 
-def _load_sd(path: str) -> dict:
-    """OpenAI's file is a TorchScript archive: a plain state dict is tried first, the archive's state dict second."""
-    try:
-        sd = torch.load(path, map_location="cpu", weights_only=True)
-        if isinstance(sd, dict):
-            return sd
-    except Exception:
-        pass
-    return torch.jit.load(path, map_location="cpu").state_dict()
-
-
-def find_file(directory: str, key: str):
-    """The first file of ``FILE_PATTERNS[key]`` in ``directory``, or None."""
-    for pat in FILE_PATTERNS[key]:
-        hits = sorted(glob.glob(os.path.join(directory, pat)))
-        if hits:
-            return hits[0]
-    return None
+# OpenAI's file is a TorchScript archive: a plain state dict is tried first, the archive's state dict second
+_load_sd = functools.partial(iqa.load_state_dict, torchscript=True)
 
 
 @dataclass
@@ -216,11 +199,8 @@ class ClipIqaWeights(_Weights):
     @classmethod
     def load(cls, directory: str) -> "ClipIqaWeights":
         """From a ``--metric_weights`` directory: ``RN50*.pt`` / ``RN50*.pth``, and ``clipiqa_text*.npz`` or CLIP's vocabulary file."""
-        model = find_file(directory, "model")
-        if model is None:
-            raise FileNotFoundError(f"no file matching {' or '.join(FILE_PATTERNS['model'])} in {directory}")
-        sd = _strip(_load_sd(model))
-        npz, vocab = find_file(directory, "text"), find_file(directory, "vocab")
+        sd = _strip(_load_sd(find_file(directory, FILE_PATTERNS["model"])))
+        npz, vocab = find_first(directory, FILE_PATTERNS["text"]), find_first(directory, FILE_PATTERNS["vocab"])
         if npz is not None:
             with np.load(npz, allow_pickle=False) as z:
                 text = {k: z[k] for k in z.files}
@@ -282,17 +262,8 @@ def embed(W: ClipIqaWeights, images: torch.Tensor) -> torch.Tensor:
     return ops.clip_attnpool_f32(features(W, [ops.percep_prep_f32(images, 1.0, 0.0, CLIP_MEAN, CLIP_STD)]), W.attn)
 
 
-def _images(images: torch.Tensor, device=None) -> torch.Tensor:
-    if images.dim() == 3:                                        # one [C,H,W] image
-        images = images[None]
-    x = _as_nchw(images, "auto")
-    if x.shape[1] not in (1, 3):
-        raise ValueError(f"clipiqa: images must have 1 or 3 channels, got shape {tuple(images.shape)}")
-    if min(x.shape[2:]) < MIN_SIDE:
-        raise ValueError(f"clipiqa: images of {x.shape[2]} x {x.shape[3]} are too small; the minimum side is {MIN_SIDE}")
-    if not x.is_cuda:
-        x = x.to(device if device is not None else torch.device("cuda", torch.cuda.current_device()))
-    return x if x.dtype in (torch.uint8, torch.float32) else x.float()
+def _images(x: torch.Tensor, device=None) -> torch.Tensor:
+    return iqa.images(x, "clipiqa", (MIN_SIDE, MIN_SIDE), FLOAT32_DTYPES, device)
 
 
 def clipiqa(W: ClipIqaWeights, pred: torch.Tensor, group: int | None = None, want_embedding: bool = False):
@@ -303,35 +274,22 @@ def clipiqa(W: ClipIqaWeights, pred: torch.Tensor, group: int | None = None, wan
         raise TypeError(f"clipiqa: weights must be ClipIqaWeights, got {type(W).__name__}")
     x = _images(pred)
     W = W.to(x.device)
-    N = x.shape[0]
-    g = group_size(x.shape[2], x.shape[3]) if group is None else max(1, int(group))
-    emb = torch.empty(N, OUTPUT_DIM, dtype=torch.float32, device=x.device)
+    emb = torch.empty(x.shape[0], OUTPUT_DIM, dtype=torch.float32, device=x.device)
+
+    def per_group(i, j):
+        emb[i:j] = embed(W, x[i:j])
+
+    for_groups(x.shape[0], group, group_size(x.shape[2], x.shape[3]), COUNTERS, x.device, per_group)
     with torch.cuda.device(x.device):
-        for i in range(0, N, g):
-            emb[i:i + g] = embed(W, x[i:i + g])
-            COUNTERS["groups"] += 1
         out = ops.clipiqa_score(emb, W.text[0], W.logit_scale)
     return (out, emb) if want_embedding else out
 
 
-class ClipIqaMetric(torch.nn.Module):
+class ClipIqaMetric(GpuMetric):
     """pyiqa-style metric object: ``metric(pred)`` with [N,C,H,W] images in [0,1] (host or device) -> [N] fp64 CLIP-IQA scores."""
 
-    lower_better = False
-
     def __init__(self, weights: ClipIqaWeights):
-        super().__init__()
-        if not isinstance(weights, ClipIqaWeights):
-            raise TypeError("create_metric('clipiqa'): weights must be a dove_amd.clipiqa.ClipIqaWeights")
-        self.metric_name, self.weights = "clipiqa", weights
-        self.register_buffer("_anchor", torch.empty(0), persistent=False)   # follows .to(device)
-
-    @property
-    def device(self) -> torch.device:
-        return self._anchor.device if self._anchor.is_cuda else torch.device("cuda", torch.cuda.current_device())
-
-    def forward(self, pred: torch.Tensor, ref=None) -> torch.Tensor:
-        return clipiqa(self.weights, pred.to(self.device))
+        super().__init__("clipiqa", False, False, clipiqa, weights, ClipIqaWeights)
 
 
 # --------------------------------------------------------------- the text side ---------------------------------------------------------------
@@ -437,7 +395,6 @@ def save_text(path: str, features, prompts, logit_scale: float) -> None:
 
 
 def main(argv=None):
-    from .niqe import _list_images, _load_image
     ap = argparse.ArgumentParser(description="CLIP-IQA on the GPU (dove_amd): make the text features of the prompts, or score images")
     sub = ap.add_subparsers(dest="cmd", required=True)
     t = sub.add_parser("text", help="run CLIP's text tower over the prompt pairs once and save the features")
@@ -458,13 +415,7 @@ def main(argv=None):
         save_text(args.out, feats.numpy(), [p for pair in pairs for p in pair], float(sd["logit_scale"]))
         print(f"text features of {len(pairs)} prompt pairs -> {args.out}")
         return feats
-    W = ClipIqaWeights.load(args.metric_weights)
-    scores = {os.path.basename(p): float(clipiqa(W, _load_image(p))[0]) for p in _list_images(args.pred)}
-    for name, v in scores.items():
-        print(f"{name}: {v:.4f}")
-    if scores:
-        print(f"average: {float(np.mean(list(scores.values()))):.4f}")
-    return scores
+    return score_folder(args, lambda a: ClipIqaWeights.load(a.metric_weights), clipiqa)
 
 
 if __name__ == "__main__":

@@ -7,10 +7,8 @@ same JSON (``metrics_<names>.json``: per_sample {clip: {metric: round(value, 4)}
 Inputs are PNG/JPG folders, single images, ``.npy`` clips (uint8 [F,H,W,3]) and ``.y4m`` files (YUV4MPEG2, read as bt601 with the
 stream's range tag; dove_amd.y4m); mp4 decoding is not provided.  ``--metrics``
 defaults to ``psnr,ssim`` (the reference's default also lists clipiqa, which needs ``--metric_weights``).  ``--metric_weights DIR`` adds
-``lpips``, ``lpips-vgg`` and ``dists`` from the checkpoints in that directory (dove_amd.percep); a file that is absent
-raises FileNotFoundError.  The same directory holds the model of the no-reference ``niqe`` (``niqe_modelparameters*.mat``, then
-``niqe*.npz``; dove_amd.niqe, INTEGRATION.md 1i) and the files of the no-reference ``clipiqa`` (``RN50*.pt`` and ``clipiqa_text*.npz``;
-dove_amd.clipiqa) and the checkpoint of the no-reference ``musiq`` (``musiq*.pth``; dove_amd.musiq).
+the metrics that ``dove_amd.metrics.REGISTRY`` declares with weights, the network and the no-reference ones, each from its files in that
+directory (``--help`` lists them with their INTEGRATION.md sections); a file that is absent raises FileNotFoundError.
 Without ``--gt`` the no-reference metrics are computed on the predictions alone and
 written to the same JSON, as in the reference (its ``--gt`` is "optional for NR-IQA"); a clip is skipped only when no no-reference metric
 was asked for.  Without the flag a metric other than psnr / ssim fails to initialise with a message, as a pyiqa metric that
@@ -26,8 +24,6 @@ import torch
 
 from . import metrics as M
 from . import prepost
-
-FR_METRICS = ["psnr", "ssim", "lpips", "dists"]          # eval_metrics.py's full-reference list
 
 
 def load_sequence(path: str) -> torch.Tensor:
@@ -74,15 +70,11 @@ def init_models(metrics, device=None, weights=None):
 
 
 def load_weights(metrics, directory):
-    """Weights of the network metrics and the NIQE model among ``metrics`` from ``--metric_weights`` -> {metric: weights}; without a directory, none (the
-    metrics then fail to initialise, as before).  A file that is absent raises FileNotFoundError."""
+    """Weights of the registered metrics among ``metrics`` that need some, from ``--metric_weights`` -> {metric: weights}; without a
+    directory, none (the metrics then fail to initialise, as before).  A file that is absent raises FileNotFoundError."""
     if not directory:
         return {}
-    from . import clipiqa, musiq, niqe, percep
-    loaders = {"niqe": niqe.load_model, "clipiqa": clipiqa.ClipIqaWeights.load, "musiq": musiq.MusiqWeights.load}
-    out = {m: percep.load_metric_weights(directory, m) for m in metrics if m in M.NETWORK_METRICS}
-    out.update({m: loaders[m](directory) for m in metrics if m in M.NR_METRICS})
-    return out
+    return {m: M.REGISTRY[m].load(directory) for m in metrics if m in M.metric_names(M.NETWORK, M.NR)}
 
 
 def process(gt_root, pred_root, out_path, metrics, batch_mode=False, crop=0, test_y_channel=False, is_center=False,
@@ -100,7 +92,7 @@ def process(gt_root, pred_root, out_path, metrics, batch_mode=False, crop=0, tes
             print(f"Skipping {name}: no matching GT file.")
             continue
         try:
-            nr = [m for m in models if m in M.NR_METRICS]
+            nr = [m for m in models if m in M.metric_names(M.NR)]
             if gt_files is None:
                 if not nr:
                     print(f"Skipping {name}: GT is not provided and no NR-IQA metrics found.")
@@ -110,7 +102,7 @@ def process(gt_root, pred_root, out_path, metrics, batch_mode=False, crop=0, tes
                 continue
             pred = load_sequence(pred_files[name])
             gt = load_sequence(gt_files[name])
-            fr = [m for m in models if m in FR_METRICS or m in weights]
+            fr = [m for m in models if m in M.metric_names(M.FR) or m in weights]
             # batch_mode and per-frame mode both average the per-frame values of the clip; one launch covers all frames either way
             vals = M.clip_metrics(pred, gt, fr, crop=crop, test_y_channel=test_y_channel, is_center=is_center, name=name,
                                   weights=weights) if fr else {}
@@ -139,19 +131,18 @@ def process(gt_root, pred_root, out_path, metrics, batch_mode=False, crop=0, tes
 
 def main(argv=None):
     parser = argparse.ArgumentParser(description="PSNR / SSIM of SR results against ground truth on the GPU (dove_amd)")
-    parser.add_argument("--gt", type=str, default="", help="Path to GT folder (optional for the no-reference niqe, clipiqa and musiq)")
+    parser.add_argument("--gt", type=str, default="", help=f"Path to GT folder (optional for the no-reference {M.name_list(M.metric_names(M.NR))})")
     parser.add_argument("--pred", type=str, required=True, help="Path to predicted results folder")
     parser.add_argument("--out", type=str, default="", help="Path to save JSON output (as directory); default: --pred")
-    parser.add_argument("--metrics", type=str, default="psnr,ssim", help="Comma-separated list of metrics: psnr,ssim")
+    parser.add_argument("--metrics", type=str, default="psnr,ssim",
+                        help=f"Comma-separated list of metrics: {','.join(M.metric_names(M.FR))}; with --metric_weights also "
+                             f"{','.join(M.metric_names(M.NETWORK, M.NR))}")
     parser.add_argument("--batch_mode", action="store_true", help="accepted; gives the same values as per-frame mode")
     parser.add_argument("--crop", type=int, default=0, help="Crop border size for PSNR/SSIM")
     parser.add_argument("--test_y_channel", action="store_true", help="Use Y channel for PSNR/SSIM")
     parser.add_argument("--is_center", action="store_true", help="Use center crop for PSNR/SSIM")
     parser.add_argument("--metric_weights", type=str, default="",
-                        help="directory with the checkpoints of lpips / lpips-vgg / dists (alexnet*.pth, vgg16*.pth, LPIPS_v0.1_alex*.pth, "
-                             "LPIPS_v0.1_vgg*.pth, DISTS_weights*.pth), the model of niqe (niqe_modelparameters*.mat or niqe*.npz) and the files of "
-                             "clipiqa (RN50*.pt, clipiqa_text*.npz) and the checkpoint of musiq (musiq*.pth); "
-                             "without it these metrics are not computed")
+                        help=f"directory with the files of {M.weights_help()}; without it these metrics are not computed")
     args = parser.parse_args(argv)
     out = args.out or args.pred
     metric_list = [m.strip().lower() for m in args.metrics.split(",")]

@@ -2,12 +2,11 @@
 
 Three surfaces:
   - ``fr_metrics(pred, ref, psnr=True, ssim=True, rgb_to_y=False)``: per-image fp64 values of a batch of strided views;
-  - ``create_metric(name)``: pyiqa's ``create_metric`` surface for 'psnr' and 'ssim', so the reference's metric code runs with
-    ``import dove_amd.metrics as pyiqa``; ``create_metric(name, weights=W)`` gives 'lpips', 'lpips-vgg' and 'dists' from user-supplied
-    checkpoints (dove_amd.percep) and the no-reference 'niqe' from a user-supplied pristine model (dove_amd.niqe.NiqeModel) and 'clipiqa'
-    from a user-supplied CLIP RN50 checkpoint (dove_amd.clipiqa.ClipIqaWeights) and 'musiq' from a user-supplied MUSIQ checkpoint
-    (dove_amd.musiq.MusiqWeights), all called as ``metric(pred)``; any other name, or one of these without weights, raises
-    ``NotImplementedError``;
+  - ``create_metric(name)``: pyiqa's ``create_metric`` surface, so the reference's metric code runs with ``import dove_amd.metrics as
+    pyiqa``.  ``REGISTRY`` declares every metric once, in the order of the command lines' lists: the full-reference metrics computed from
+    the images alone, and the ones made by ``create_metric(name, weights=W)`` from files the user supplies (a network metric is called as
+    ``metric(pred, ref)``, a no-reference one as ``metric(pred)``); any other name, or one of these without weights, raises
+    ``NotImplementedError``.  The evaluation tool and the inference command line read the same table;
   - ``clip_metrics(pred_u8, gt_u8, names, crop, test_y_channel, is_center)``: the per-clip logic of eval_metrics.py (match_resolution,
     crop_border, rgb_to_y, mean over frames), as views on the device; ``nr_clip_metrics(pred_u8, names, weights)`` is its ground-truth-free
     half (the no-reference metrics on the predictions as they are).
@@ -19,32 +18,86 @@ eval_metrics.py's ``--test_y_channel`` first maps RGB to y = 0.257 r + 0.504 g +
 the one-channel branch)."""
 from __future__ import annotations
 
+import functools
+import importlib
+from dataclasses import dataclass
+from typing import Callable
+
 import torch
 
 from . import lib as L
 from . import ops
+from .iqa import GpuMetric, find_first
+from .iqa import as_nchw as _as_nchw            # the name other modules and tests know it by
 
-FR_METRICS = ("psnr", "ssim")
-NETWORK_METRICS = ("lpips", "lpips-vgg", "dists")       # computed by dove_amd.percep when the caller passes weights
-NR_METRICS = ("niqe", "clipiqa", "musiq")               # no-reference: dove_amd.niqe (NiqeModel), .clipiqa (ClipIqaWeights), .musiq (MusiqWeights)
+FR, NETWORK, NR = "full-reference", "full-reference network", "no-reference"
+
+
+@dataclass(frozen=True)
+class MetricSpec:
+    """One metric, declared once.  ``build(weights=W)`` (``build()`` for kind FR) makes the metric object, ``load(directory)`` its weights
+    from a ``--metric_weights`` directory, ``probe(directory)`` says cheaply whether the main file is there (without one, ``load`` is the
+    only check); ``patterns`` are the files ``load`` looks for and ``section`` is where INTEGRATION.md describes them."""
+    name: str
+    kind: str
+    lower_better: bool
+    build: Callable
+    load: Callable | None = None
+    probe: Callable | None = None
+    patterns: tuple = ()
+    section: str = ""
+
+
+def _late(module: str, attr: str, **bound) -> Callable:
+    """``dove_amd.<module>.<attr>`` (``attr`` may be dotted), imported when it is first called: this module loads without the metric
+    modules."""
+    def call(*args, **kwargs):
+        return functools.reduce(getattr, attr.split("."), importlib.import_module(f"{__package__}.{module}"))(*args, **bound, **kwargs)
+    return call
+
+
+def _has(*patterns) -> Callable:
+    return lambda directory: find_first(directory, patterns) is not None
+
+
+_PERCEP = {"lpips": ("alexnet*.pth", "LPIPS_v0.1_alex*.pth"), "lpips-vgg": ("vgg16*.pth", "LPIPS_v0.1_vgg*.pth"),
+           "dists": ("vgg16*.pth", "DISTS_weights*.pth")}
+REGISTRY: dict = {s.name: s for s in (
+    *(MetricSpec(n, FR, False, lambda n=n: FRMetric(n)) for n in ("psnr", "ssim")),
+    *(MetricSpec(n, NETWORK, True, _late("percep", "PerceptualMetric", name=n), _late("percep", "load_metric_weights", name=n),
+                 patterns=p, section="1h") for n, p in _PERCEP.items()),
+    MetricSpec("niqe", NR, True, _late("niqe", "NiqeMetric"), _late("niqe", "load_model"),
+               patterns=("niqe_modelparameters*.mat", "niqe*.npz"), section="1i"),
+    MetricSpec("clipiqa", NR, False, _late("clipiqa", "ClipIqaMetric"), _late("clipiqa", "ClipIqaWeights.load"), _has("RN50*.pt", "RN50*.pth"),
+               patterns=("RN50*.pt", "RN50*.pth", "clipiqa_text*.npz", "bpe_simple_vocab_16e6.txt*"), section="1j"),
+    MetricSpec("musiq", NR, False, _late("musiq", "MusiqMetric"), _late("musiq", "MusiqWeights.load"), _has("musiq*.pth"),
+               patterns=("musiq*.pth",), section="1k"),
+)}
+
+
+def metric_names(*kinds) -> tuple:
+    """The registered names of the given kinds (all without any), in registry order."""
+    return tuple(n for n, s in REGISTRY.items() if not kinds or s.kind in kinds)
+
+
+FR_METRICS, NETWORK_METRICS, NR_METRICS = metric_names(FR), metric_names(NETWORK), metric_names(NR)      # as first registered
+
+
+def name_list(names) -> str:
+    """'a', 'a and b', 'a, b and c'."""
+    names = list(names)
+    return " and ".join(filter(None, (", ".join(names[:-1]), names[-1]))) if names else ""
+
+
+def weights_help() -> str:
+    """What a ``--metric_weights`` directory holds, for the command lines' help texts."""
+    return "; ".join(f"{n}: {', '.join(s.patterns)} (INTEGRATION.md {s.section})" for n, s in REGISTRY.items() if s.kind != FR)
 
 
 def _unsupported(name: str) -> NotImplementedError:
-    return NotImplementedError(f"metric '{name}': dove_amd computes the full-reference metrics {', '.join(FR_METRICS)} on the GPU; "
-                               "the other pyiqa metrics (lpips, dists, clipiqa, musiq, maniqa, niqe, ...) need network weights and are "
+    return NotImplementedError(f"metric '{name}': dove_amd computes the full-reference metrics {', '.join(metric_names(FR))} on the GPU; "
+                               f"the other pyiqa metrics ({', '.join(metric_names(NETWORK, NR))}, ...) need network weights and are "
                                "not provided - use pyiqa itself for them")
-
-
-def _as_nchw(t: torch.Tensor, layout: str) -> torch.Tensor:
-    if t.dim() != 4:
-        raise ValueError(f"expected a 4-D image batch, got shape {tuple(t.shape)}")
-    if layout == "auto":
-        layout = "nhwc" if t.dtype == torch.uint8 and t.shape[3] in (1, 3) and t.shape[1] not in (1, 3) else "nchw"
-    if layout == "nhwc":
-        return t.permute(0, 3, 1, 2)
-    if layout != "nchw":
-        raise ValueError(f"layout must be 'auto', 'nchw' or 'nhwc', got {layout!r}")
-    return t
 
 
 def fr_metrics(pred: torch.Tensor, ref: torch.Tensor, psnr: bool = True, ssim: bool = True, rgb_to_y: bool = False,
@@ -64,64 +117,33 @@ def fr_metrics(pred: torch.Tensor, ref: torch.Tensor, psnr: bool = True, ssim: b
     return (out[:, 0] if psnr else None), (out[:, 1] if ssim else None)
 
 
-class FRMetric(torch.nn.Module):
-    """pyiqa-style metric object for 'psnr' / 'ssim': ``metric(pred, ref)`` with [N,C,H,W] images in [0,1] -> [N] fp64 scores.
-
-    Like pyiqa's InferenceModel, the inputs are moved to the metric's device first: the device given to ``.to()``, or the current HIP
-    device while the metric has not been moved to one (there is no CPU path).  The reference's in-process loop passes host frames."""
-
-    lower_better = False
+class FRMetric(GpuMetric):
+    """pyiqa-style metric object for 'psnr' / 'ssim': ``metric(pred, ref)`` with [N,C,H,W] images in [0,1] -> [N] fp64 scores."""
 
     def __init__(self, name: str):
-        super().__init__()
-        self.metric_name = name
-        self.register_buffer("_anchor", torch.empty(0), persistent=False)   # follows .to(device)
-
-    @property
-    def device(self) -> torch.device:
-        return self._anchor.device if self._anchor.is_cuda else torch.device("cuda", torch.cuda.current_device())
-
-    def forward(self, pred: torch.Tensor, ref: torch.Tensor) -> torch.Tensor:
-        if pred.dim() == 3:                                         # pyiqa accepts a single [C,H,W] image too
-            pred, ref = pred[None], ref[None]
-        dev = self.device
-        pred, ref = pred.to(dev), ref.to(dev)
-        psnr, ssim = fr_metrics(pred, ref, psnr=self.metric_name == "psnr", ssim=self.metric_name == "ssim", layout="nchw")
-        return psnr if self.metric_name == "psnr" else ssim
+        def score(_, pred, ref):
+            psnr, ssim = fr_metrics(pred, ref, psnr=name == "psnr", ssim=name == "ssim", layout="nchw")
+            return psnr if name == "psnr" else ssim
+        super().__init__(name, False, True, score)
 
 
 def create_metric(name: str, weights=None, **kwargs):
-    """``pyiqa.create_metric`` for the full-reference metrics computed here: 'psnr' and 'ssim' with pyiqa's default options, and, given
-    ``weights`` (percep.LpipsWeights / percep.DistsWeights), 'lpips', 'lpips-vgg' and 'dists' (lower is better, [N] fp64); with
-    ``weights`` a niqe.NiqeModel, the no-reference 'niqe' (``metric(pred)``, lower is better, [N] fp64); with clipiqa.ClipIqaWeights, the
-    no-reference 'clipiqa', and with musiq.MusiqWeights the no-reference 'musiq' (``metric(pred)``, higher is better, [N] fp64)."""
+    """``pyiqa.create_metric`` for the metrics of ``REGISTRY``, with pyiqa's default options: the full-reference ones as they are, the
+    others given ``weights`` (what the spec's ``load`` returns).  Every metric object returns [N] fp64; ``lower_better`` says which way."""
     key = name.strip().lower()
-    if weights is not None:
-        if key not in NETWORK_METRICS + NR_METRICS:
-            raise NotImplementedError(f"create_metric('{name}', weights=...): weights belong to {', '.join(NETWORK_METRICS + NR_METRICS)}")
-        if kwargs:
-            raise NotImplementedError(f"create_metric('{name}', {sorted(kwargs)}): only pyiqa's default options are implemented")
-        if key == "clipiqa":
-            from . import clipiqa
-            return clipiqa.ClipIqaMetric(weights)
-        if key == "musiq":
-            from . import musiq
-            return musiq.MusiqMetric(weights)
-        if key in NR_METRICS:
-            from . import niqe
-            return niqe.NiqeMetric(weights)
-        from . import percep
-        return percep.PerceptualMetric(key, weights)
-    if key not in FR_METRICS:
+    spec = REGISTRY.get(key)
+    if weights is not None and (spec is None or spec.kind == FR):
+        raise NotImplementedError(f"create_metric('{name}', weights=...): weights belong to {', '.join(metric_names(NETWORK, NR))}")
+    if weights is None and (spec is None or spec.kind != FR):
         raise _unsupported(name)
     if kwargs:
         raise NotImplementedError(f"create_metric('{name}', {sorted(kwargs)}): only pyiqa's default options are implemented")
-    return FRMetric(key)
+    return spec.build() if weights is None else spec.build(weights=weights)
 
 
 def list_models(metric_mode=None):
-    """pyiqa.list_models: the metrics this module provides."""
-    return list(FR_METRICS) if metric_mode in (None, "FR") else []
+    """pyiqa.list_models: the metrics this module provides without weights."""
+    return list(metric_names(FR)) if metric_mode in (None, "FR") else []
 
 
 def nr_clip_metrics(pred_u8: torch.Tensor, names, weights: dict) -> dict:
@@ -129,7 +151,7 @@ def nr_clip_metrics(pred_u8: torch.Tensor, names, weights: dict) -> dict:
     match_resolution, no crop_border, no rgb_to_y.  ``pred_u8``: [F,H,W,3] uint8 frames (a host tensor is uploaded as uint8)."""
     vals = {}
     for n in names:
-        if n not in NR_METRICS or n not in weights:
+        if n not in metric_names(NR) or n not in weights:
             raise _unsupported(n)
         dev = pred_u8.device if pred_u8.is_cuda else torch.device("cuda")
         vals[n] = float(create_metric(n, weights=weights[n])(pred_u8.to(dev).permute(0, 3, 1, 2)).mean())
@@ -171,14 +193,14 @@ def rgb_to_y(frames: torch.Tensor) -> torch.Tensor:
 def clip_metrics(pred_u8: torch.Tensor, gt_u8: torch.Tensor, names, crop: int = 0, test_y_channel: bool = False,
                  is_center: bool = False, name: str | None = None, weights: dict | None = None) -> dict:
     """Per-clip metrics as eval_metrics.py computes them -> {metric: mean over frames of the per-frame value}: the full-reference ones,
-    and 'niqe' / 'clipiqa' / 'musiq' (given their weights in ``weights``) on the uncropped predictions (``crop`` and ``test_y_channel`` do not apply to them).
+    and the no-reference ones (given their weights in ``weights``) on the uncropped predictions (``crop`` and ``test_y_channel`` do not apply to them).
 
     ``pred_u8`` / ``gt_u8``: [F,H,W,3] uint8 frames (a host tensor is uploaded as uint8).  Steps of the reference: match_resolution
     (common frame count, top-left or centre crop to the common H x W), crop_border, optional rgb_to_y; all of them are views."""
     names = [n.strip().lower() for n in (names.split(",") if isinstance(names, str) else names)]
     weights = weights or {}
     for n in names:
-        if n not in FR_METRICS and n not in weights:
+        if n not in metric_names(FR) and n not in weights:
             raise _unsupported(n)
     dev = pred_u8.device if pred_u8.is_cuda else (gt_u8.device if gt_u8.is_cuda else torch.device("cuda"))
     pred_u8, gt_u8 = pred_u8.to(dev), gt_u8.to(dev)
@@ -189,8 +211,8 @@ def clip_metrics(pred_u8: torch.Tensor, gt_u8: torch.Tensor, names, crop: int = 
     if "psnr" in names or "ssim" in names:
         vals["psnr"], vals["ssim"] = fr_metrics(pred, gt, psnr="psnr" in names, ssim="ssim" in names, rgb_to_y=test_y_channel,
                                                 layout="nhwc")
-    nr = nr_clip_metrics(full, [n for n in names if n in NR_METRICS], weights)
-    net = [n for n in names if n not in FR_METRICS + NR_METRICS]
+    nr = nr_clip_metrics(full, [n for n in names if n in metric_names(NR)], weights)
+    net = [n for n in names if n not in metric_names(FR, NR)]
     if net:
         # the reference hands the networks the same cropped (and, with --test_y_channel, one-channel) images as PSNR / SSIM;
         # ``weights`` of a user-supplied checkpoint make the metric, so ``names`` without them were refused above

@@ -28,18 +28,16 @@ grouping.
 from __future__ import annotations
 
 import argparse
-import glob
 import math
-import os
 import zlib
 from dataclasses import dataclass, field
 
 import numpy as np
 import torch
 
-from . import ops
+from . import iqa, ops
 from .flow import pack_conv_weight
-from .metrics import _as_nchw
+from .iqa import ACTIVATION_BUDGET, GpuMetric, find_file, for_groups, load_state_dict, score_folder
 from .percep import _checked, _strip, _Weights
 
 PATCH, HASH_GRID = 32, 10
@@ -56,7 +54,6 @@ FILE_PATTERN = "musiq*.pth"
 # and conv2's output (8 x 8 x 64): 4096 + 16384 + 16384 + 4096 = 40960 floats = 160 KiB.  The stem conv (its 37 x 37 x 3 frame next to the
 # 16 x 16 x 64 output) needs 80 KiB, the transformer 3 K floats.  Measured with tools/musiq_bench.py (docs/kernels.md).
 TOKEN_FLOATS = 40960
-ACTIVATION_BUDGET = 4 << 30
 WEIGHT_DRAW = 0                                     # random_musiq_state's generator draw: see there
 COUNTERS = {"groups": 0}                            # groups walked, for tests and tools
 
@@ -174,19 +171,6 @@ def standardise(w: torch.Tensor) -> torch.Tensor:
     return (w - m) / (s + STD_EPS)
 
 
-def _load_sd(path: str) -> dict:
-    sd = torch.load(path, map_location="cpu", weights_only=True)
-    if isinstance(sd, dict) and isinstance(sd.get("params"), dict):
-        sd = sd["params"]
-    return sd
-
-
-def find_file(directory: str):
-    """The first ``musiq*.pth`` of ``directory``, or None."""
-    hits = sorted(glob.glob(os.path.join(directory, FILE_PATTERN))) if directory else []
-    return hits[0] if hits else None
-
-
 @dataclass
 class MusiqWeights(_Weights):
     """``convs``: the standardised stem convs (weight [k,k,cin,cout], no bias); ``params``: every other tensor by a short name."""
@@ -224,10 +208,7 @@ class MusiqWeights(_Weights):
     @classmethod
     def load(cls, directory: str) -> "MusiqWeights":
         """From a ``--metric_weights`` directory: the first ``musiq*.pth`` (pyiqa's checkpoint; a top-level ``params`` is unwrapped)."""
-        path = find_file(directory)
-        if path is None:
-            raise FileNotFoundError(f"no file matching {FILE_PATTERN} in {directory}")
-        return cls.from_state_dict(_load_sd(path))
+        return cls.from_state_dict(load_state_dict(find_file(directory, FILE_PATTERN)))
 
     def to(self, device):
         new = super().to(device)
@@ -294,71 +275,40 @@ def features(W: MusiqWeights, images: torch.Tensor) -> torch.Tensor:
     return ops.layernorm_f32(x[:, 0], p["encoder_norm.weight"], p["encoder_norm.bias"], LN_EPS)
 
 
-def _images(images: torch.Tensor, device=None) -> torch.Tensor:
-    if images.dim() == 3:                                        # one [C,H,W] image
-        images = images[None]
-    x = _as_nchw(images, "auto")
-    if x.shape[1] not in (1, 3):
-        raise ValueError(f"musiq: images must have 1 or 3 channels, got shape {tuple(images.shape)}")
-    if not x.is_cuda:
-        x = x.to(device if device is not None else torch.device("cuda", torch.cuda.current_device()))
-    return x if x.dtype in (torch.uint8, torch.float32, torch.bfloat16) else x.float()
-
-
 def musiq(W: MusiqWeights, pred: torch.Tensor, group: int | None = None, want_features: bool = False):
     """MUSIQ per image -> float64 [N] on the device, higher is better.  ``pred``: [N,C,H,W] float in [0,1] or uint8 (any strides, C in
     {1, 3}; one channel is repeated), or [F,H,W,3] uint8 frames; a host tensor is uploaded.  ``group``: frames per batch (default: from
     the budget).  ``want_features``: also return the float32 [N,384] normalised token 0."""
     if not isinstance(W, MusiqWeights):
         raise TypeError(f"musiq: weights must be MusiqWeights, got {type(W).__name__}")
-    x = _images(pred)
+    x = iqa.images(pred, "musiq", dtypes=(torch.uint8, torch.float32, torch.bfloat16))      # any size from 1 x 1; the patch kernel reads bfloat16 too
     W = W.to(x.device)
-    N = x.shape[0]
-    g = group_size(x.shape[2], x.shape[3]) if group is None else max(1, int(group))
-    feats = torch.empty(N, DIM, dtype=torch.float32, device=x.device)
+    feats = torch.empty(x.shape[0], DIM, dtype=torch.float32, device=x.device)
+
+    def per_group(i, j):
+        feats[i:j] = features(W, x[i:j])
+
+    for_groups(x.shape[0], group, group_size(x.shape[2], x.shape[3]), COUNTERS, x.device, per_group)
     with torch.cuda.device(x.device):
-        for i in range(0, N, g):
-            feats[i:i + g] = features(W, x[i:i + g])
-            COUNTERS["groups"] += 1
         out = ops.musiq_score(feats, W.params["head.weight"], W.params["head.bias"])
     return (out, feats) if want_features else out
 
 
-class MusiqMetric(torch.nn.Module):
+class MusiqMetric(GpuMetric):
     """pyiqa-style metric object: ``metric(pred)`` with [N,C,H,W] images in [0,1] (host or device) -> [N] fp64 MUSIQ scores."""
 
-    lower_better = False
-
     def __init__(self, weights: MusiqWeights):
-        super().__init__()
-        if not isinstance(weights, MusiqWeights):
-            raise TypeError("create_metric('musiq'): weights must be a dove_amd.musiq.MusiqWeights")
-        self.metric_name, self.weights = "musiq", weights
-        self.register_buffer("_anchor", torch.empty(0), persistent=False)   # follows .to(device)
-
-    @property
-    def device(self) -> torch.device:
-        return self._anchor.device if self._anchor.is_cuda else torch.device("cuda", torch.cuda.current_device())
-
-    def forward(self, pred: torch.Tensor, ref=None) -> torch.Tensor:
-        return musiq(self.weights, pred.to(self.device))
+        super().__init__("musiq", False, False, musiq, weights, MusiqWeights)
 
 
 def main(argv=None):
-    from .niqe import _list_images, _load_image
     ap = argparse.ArgumentParser(description="MUSIQ on the GPU (dove_amd): score images")
     sub = ap.add_subparsers(dest="cmd", required=True)
     s = sub.add_parser("score", help="score every image of a folder")
     s.add_argument("--pred", required=True, help="folder of images")
     s.add_argument("--metric_weights", required=True, help=f"directory with {FILE_PATTERN}")
     args = ap.parse_args(argv)
-    W = MusiqWeights.load(args.metric_weights)
-    scores = {os.path.basename(p): float(musiq(W, _load_image(p))[0]) for p in _list_images(args.pred)}
-    for name, v in scores.items():
-        print(f"{name}: {v:.4f}")
-    if scores:
-        print(f"average: {float(np.mean(list(scores.values()))):.4f}")
-    return scores
+    return score_folder(args, lambda a: MusiqWeights.load(a.metric_weights), musiq)
 
 
 if __name__ == "__main__":

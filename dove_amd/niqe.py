@@ -17,16 +17,17 @@ frames; H, W >= 96.  Everything on the device is fp64; the 36 x 36 pseudo-invers
 from __future__ import annotations
 
 import argparse
-import glob
 import os
 
 import numpy as np
 import torch
 
-from . import ops
+from . import iqa, ops
+from .iqa import IMAGE_EXTENSIONS, GpuMetric, find_file, score_folder
+from .iqa import list_images as _list_images
+from .iqa import load_image as _load_image
 
 FILE_PATTERNS = ("niqe_modelparameters*.mat", "niqe*.npz")       # searched in this order in a --metric_weights directory
-IMAGE_EXTENSIONS = (".png", ".jpg", ".jpeg", ".bmp")
 
 
 class NiqeModel:
@@ -66,11 +67,7 @@ class NiqeModel:
 
 
 def find_model_file(directory: str) -> str:
-    for pattern in FILE_PATTERNS:
-        hits = sorted(glob.glob(os.path.join(directory, pattern)))
-        if hits:
-            return hits[0]
-    raise FileNotFoundError(f"no file matching {' or '.join(FILE_PATTERNS)} in {directory}")
+    return find_file(directory, FILE_PATTERNS)
 
 
 def load_model(directory: str) -> NiqeModel:
@@ -78,18 +75,8 @@ def load_model(directory: str) -> NiqeModel:
     return NiqeModel.load(find_model_file(directory))
 
 
-def _images(images: torch.Tensor, device=None) -> torch.Tensor:
-    from .metrics import _as_nchw
-    if images.dim() == 3:                                        # one [C,H,W] image
-        images = images[None]
-    x = _as_nchw(images, "auto")
-    if x.shape[1] not in (1, 3):
-        raise ValueError(f"niqe: images must have 1 or 3 channels, got shape {tuple(images.shape)}")
-    if x.shape[2] < 96 or x.shape[3] < 96:
-        raise ValueError(f"niqe: H and W must be at least 96 (one 96 x 96 block), got {x.shape[2]} x {x.shape[3]}")
-    if not x.is_cuda:
-        x = x.to(device if device is not None else torch.device("cuda", torch.cuda.current_device()))
-    return x
+def _images(x: torch.Tensor, device=None) -> torch.Tensor:
+    return iqa.images(x, "niqe", (96, 96), device=device)           # one 96 x 96 block at least; every dtype is read as it is
 
 
 def features(images: torch.Tensor, device=None):
@@ -110,11 +97,6 @@ def niqe(model: NiqeModel, images: torch.Tensor, device=None) -> torch.Tensor:
     return torch.tensor(out, dtype=torch.float64, device=x.device)
 
 
-def _load_image(path: str) -> torch.Tensor:
-    from PIL import Image
-    return torch.from_numpy(np.asarray(Image.open(path).convert("RGB")).copy())[None]
-
-
 def fit(paths_or_tensors, sharpness: float = 0.75, device=None) -> NiqeModel:
     """The pristine model of a set of images (paths, or tensors as ``features`` takes them; sizes may differ): of every image the blocks
     whose sharpness exceeds ``sharpness`` x that image's largest are kept; mu and cov (divisor n-1) over the kept NaN-free blocks."""
@@ -132,28 +114,11 @@ def fit(paths_or_tensors, sharpness: float = 0.75, device=None) -> NiqeModel:
     return NiqeModel(rows.mean(axis=0), np.cov(rows, rowvar=False))
 
 
-class NiqeMetric(torch.nn.Module):
+class NiqeMetric(GpuMetric):
     """pyiqa-style metric object: ``metric(pred)`` with [N,C,H,W] images in [0,1] (host or device) -> [N] fp64 NIQE scores."""
 
-    lower_better = True
-
     def __init__(self, weights: NiqeModel):
-        super().__init__()
-        if not isinstance(weights, NiqeModel):
-            raise TypeError("create_metric('niqe'): weights must be a dove_amd.niqe.NiqeModel")
-        self.metric_name, self.weights = "niqe", weights
-        self.register_buffer("_anchor", torch.empty(0), persistent=False)   # follows .to(device)
-
-    @property
-    def device(self) -> torch.device:
-        return self._anchor.device if self._anchor.is_cuda else torch.device("cuda", torch.cuda.current_device())
-
-    def forward(self, pred: torch.Tensor, ref=None) -> torch.Tensor:
-        return niqe(self.weights, pred.to(self.device))
-
-
-def _list_images(directory: str):
-    return sorted(os.path.join(directory, f) for f in os.listdir(directory) if f.lower().endswith(IMAGE_EXTENSIONS))
+        super().__init__("niqe", True, False, niqe, weights, NiqeModel)
 
 
 def main(argv=None):
@@ -175,13 +140,7 @@ def main(argv=None):
         model.save(args.out)
         print(f"fitted on {len(paths)} images -> {args.out}")
         return model
-    model = NiqeModel.load(args.model)
-    scores = {os.path.basename(p): float(niqe(model, _load_image(p))[0]) for p in _list_images(args.pred)}
-    for name, v in scores.items():
-        print(f"{name}: {v:.4f}")
-    if scores:
-        print(f"average: {float(np.mean(list(scores.values()))):.4f}")
-    return scores
+    return score_folder(args, lambda a: NiqeModel.load(a.model), niqe)
 
 
 if __name__ == "__main__":

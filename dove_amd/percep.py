@@ -18,18 +18,16 @@ sized so that the live activations of a group stay under ``ACTIVATION_BUDGET``; 
 """
 from __future__ import annotations
 
-import glob
 import math
-import os
 import zlib
 from dataclasses import dataclass, field
 
 import numpy as np
 import torch
 
-from . import ops
+from . import iqa, ops
 from .flow import pack_conv_weight
-from .metrics import _as_nchw
+from .iqa import ACTIVATION_BUDGET, FLOAT32_DTYPES, GpuMetric, as_nchw, find_file, for_groups, load_state_dict
 
 ALEX_CONVS = ((0, 64, 3, 11, 4, 2), (3, 192, 64, 5, 1, 2), (6, 384, 192, 3, 1, 1), (8, 256, 384, 3, 1, 1), (10, 256, 256, 3, 1, 1))
 VGG_STAGES = (((0, 64, 3), (2, 64, 64)), ((5, 128, 64), (7, 128, 128)), ((10, 256, 128), (12, 256, 256), (14, 256, 256)),
@@ -41,7 +39,6 @@ LPIPS_SHIFT, LPIPS_SCALE = (-.030, -.088, -.188), (.458, .448, .450)
 DISTS_MEAN, DISTS_STD = (.485, .456, .406), (.229, .224, .225)
 # Live fp32 activations of one trunk group.  The peak of VGG16 is conv1_2: its 64-channel input and output at full resolution, next to the
 # 3-channel images (one 720 x 1280 stage-1 map is 236 MB); of AlexNet conv1's output at 1/16 of the pixels.  4 GiB holds four 720p pairs.
-ACTIVATION_BUDGET = 4 << 30
 FILE_PATTERNS = {"alex": "alexnet*.pth", "vgg": "vgg16*.pth", "lpips-alex": "LPIPS_v0.1_alex*.pth", "lpips-vgg": "LPIPS_v0.1_vgg*.pth",
                  "dists": "DISTS_weights*.pth"}
 COUNTERS = {"groups": 0}                            # trunk groups walked, for tests and tools
@@ -112,10 +109,6 @@ def _pack_backbone(sd: dict, net: str) -> dict:
     return {n: (pack_conv_weight(sd[f"features.{n}.weight"]), sd[f"features.{n}.bias"].float().contiguous()) for n in nums}
 
 
-def _load_sd(path: str) -> dict:
-    return torch.load(path, map_location="cpu", weights_only=True)
-
-
 @dataclass
 class _Weights:
     convs: dict = field(default_factory=dict)       # features.N -> (w [kh,kw,cin,cout], bias)
@@ -155,7 +148,7 @@ class LpipsWeights(_Weights):
 
     @classmethod
     def load(cls, backbone_path: str, lin_path: str, net: str) -> "LpipsWeights":
-        return cls.from_state_dicts(_load_sd(backbone_path), _load_sd(lin_path), net)
+        return cls.from_state_dicts(load_state_dict(backbone_path), load_state_dict(lin_path), net)
 
 
 @dataclass
@@ -176,39 +169,32 @@ class DistsWeights(_Weights):
 
     @classmethod
     def load(cls, backbone_path: str, ab_path: str) -> "DistsWeights":
-        return cls.from_state_dicts(_load_sd(backbone_path), _load_sd(ab_path))
-
-
-def find_weight_file(directory: str, key: str) -> str:
-    """The file of ``FILE_PATTERNS[key]`` in ``directory`` (the names torchvision and pyiqa give their downloads)."""
-    hits = sorted(glob.glob(os.path.join(directory, FILE_PATTERNS[key])))
-    if not hits:
-        raise FileNotFoundError(f"no file matching {FILE_PATTERNS[key]} in {directory}")
-    return hits[0]
+        return cls.from_state_dicts(load_state_dict(backbone_path), load_state_dict(ab_path))
 
 
 def load_metric_weights(directory: str, name: str):
-    """Weights of metric ``name`` ('lpips', 'lpips-vgg', 'dists') from a directory of checkpoints."""
+    """Weights of metric ``name`` ('lpips', 'lpips-vgg', 'dists') from a directory of checkpoints (the names torchvision and pyiqa give
+    their downloads: ``FILE_PATTERNS``)."""
+    file = lambda key: find_file(directory, FILE_PATTERNS[key])
     if name == "lpips":
-        return LpipsWeights.load(find_weight_file(directory, "alex"), find_weight_file(directory, "lpips-alex"), "alex")
+        return LpipsWeights.load(file("alex"), file("lpips-alex"), "alex")
     if name == "lpips-vgg":
-        return LpipsWeights.load(find_weight_file(directory, "vgg"), find_weight_file(directory, "lpips-vgg"), "vgg")
+        return LpipsWeights.load(file("vgg"), file("lpips-vgg"), "vgg")
     if name == "dists":
-        return DistsWeights.load(find_weight_file(directory, "vgg"), find_weight_file(directory, "dists"))
+        return DistsWeights.load(file("vgg"), file("dists"))
     raise ValueError(f"no network weights belong to metric {name!r}")
 
 
 # ------------------------------------------------------------------- walk -------------------------------------------------------------------
 def _inputs(pred: torch.Tensor, ref: torch.Tensor, net: str, what: str):
-    p, r = _as_nchw(pred, "auto"), _as_nchw(ref, "auto")
+    p, r = as_nchw(pred, "auto"), as_nchw(ref, "auto")
     if p.shape != r.shape or p.shape[1] not in (1, 3):
         raise ValueError(f"{what}: pred {tuple(pred.shape)} and ref {tuple(ref.shape)} must be the same [N,1|3,H,W] shape")
-    if min(p.shape[2:]) < MIN_SIDE[net]:
-        raise ValueError(f"{what}: images of {p.shape[2]} x {p.shape[3]} are too small; the minimum side is {MIN_SIDE[net]}")
+    # device=t.device: a host tensor is not uploaded here; it is refused below, once its size has been checked
+    p, r = (iqa.images(t, what, (MIN_SIDE[net],) * 2, FLOAT32_DTYPES, device=t.device) for t in (p, r))
     if not (p.is_cuda and r.is_cuda) or p.device != r.device:
         raise RuntimeError(f"{what} needs both images on the same HIP device (`cuda`); there is no CPU path")
-    fix = lambda t: t if t.dtype in (torch.uint8, torch.float32) else t.float()
-    return fix(p), fix(r)
+    return p, r
 
 
 def group_size(net: str, h: int, w: int, budget: int | None = None) -> int:
@@ -242,13 +228,9 @@ def _vgg_taps(W, x, l2: bool):
 def _walk(W, pred, ref, net: str, what: str, group, per_group):
     p, r = _inputs(pred, ref, net, what)
     W = W.to(p.device)
-    N = p.shape[0]
-    out = torch.zeros(N, dtype=torch.float64, device=p.device)
-    g = group_size(net, p.shape[2], p.shape[3]) if group is None else max(1, int(group))
-    with torch.cuda.device(p.device):
-        for i in range(0, N, g):
-            per_group(W, p[i:i + g], r[i:i + g], out[i:i + g])
-            COUNTERS["groups"] += 1
+    out = torch.zeros(p.shape[0], dtype=torch.float64, device=p.device)
+    for_groups(p.shape[0], group, group_size(net, p.shape[2], p.shape[3]), COUNTERS, p.device,
+               lambda i, j: per_group(W, p[i:j], r[i:j], out[i:j]))
     return out
 
 
@@ -291,28 +273,11 @@ def dists(W: DistsWeights, pred: torch.Tensor, ref: torch.Tensor, group: int | N
     return _walk(W, pred, ref, "vgg", "dists", group, per_group)
 
 
-class PerceptualMetric(torch.nn.Module):
+class PerceptualMetric(GpuMetric):
     """pyiqa-style metric object for 'lpips', 'lpips-vgg' and 'dists': ``metric(pred, ref)`` with [N,C,H,W] images in [0,1] -> [N] fp64."""
 
-    lower_better = True
-
     def __init__(self, name: str, weights):
-        super().__init__()
-        want = DistsWeights if name == "dists" else LpipsWeights
-        if not isinstance(weights, want) or (name != "dists" and weights.net != ("vgg" if name == "lpips-vgg" else "alex")):
-            raise TypeError(f"create_metric('{name}'): weights must be {want.__name__}" +
-                            ("" if name == "dists" else f" of net '{'vgg' if name == 'lpips-vgg' else 'alex'}'"))
-        self.metric_name, self.weights = name, weights
-        self.register_buffer("_anchor", torch.empty(0), persistent=False)
-
-    @property
-    def device(self) -> torch.device:
-        return self._anchor.device if self._anchor.is_cuda else torch.device("cuda", torch.cuda.current_device())
-
-    def forward(self, pred: torch.Tensor, ref: torch.Tensor) -> torch.Tensor:
-        if pred.dim() == 3:
-            pred, ref = pred[None], ref[None]
-        dev = self.device
-        self.weights = self.weights.to(dev)
-        fn = dists if self.metric_name == "dists" else lpips
-        return fn(self.weights, pred.to(dev), ref.to(dev))
+        net = {"lpips": "alex", "lpips-vgg": "vgg"}.get(name)
+        super().__init__(name, True, True, dists if net is None else lpips, weights, DistsWeights if net is None else LpipsWeights)
+        if net is not None and weights.net != net:
+            raise TypeError(f"create_metric('{name}'): weights must be a {__name__}.LpipsWeights of net '{net}'")

@@ -260,8 +260,10 @@ def test_command_lines_name_the_missing_files(tmp_path):
         E.load_weights(["psnr", "clipiqa"], str(tmp_path))
     with pytest.raises(NotImplementedError, match=r"RN50\*\.pt"):
         cli.main(["--input_dir", str(tmp_path), "--eval_metrics", "clipiqa", "--metric_weights", str(tmp_path)])
-    with pytest.raises(NotImplementedError, match="adds lpips, lpips-vgg, dists, niqe and clipiqa"):
+    with pytest.raises(NotImplementedError, match="--metric_weights DIR adds") as e:
         cli.main(["--input_dir", str(tmp_path), "--eval_metrics", "clipiqa"])
+    added = re.split(r", | and ", str(e.value).split("--metric_weights DIR adds ")[1].rstrip(")"))
+    assert added == list(M.NETWORK_METRICS + M.NR_METRICS) and "clipiqa" in added     # every registered metric that needs weights, by name
     torch.save({}, tmp_path / "RN50.pt")                                  # accepted now: the loader is reached and names the first key
     with pytest.raises(FileNotFoundError, match="clipiqa_text"):
         cli.main(["--input_dir", str(tmp_path), "--eval_metrics", "clipiqa", "--metric_weights", str(tmp_path)])

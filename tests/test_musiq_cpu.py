@@ -183,5 +183,7 @@ def test_command_lines_name_the_missing_file(tmp_path):
         E.load_weights(["psnr", "musiq"], str(tmp_path))
     with pytest.raises(NotImplementedError, match=r"musiq\*\.pth"):
         cli.main(["--input_dir", str(tmp_path), "--eval_metrics", "musiq", "--metric_weights", str(tmp_path)])
-    with pytest.raises(NotImplementedError, match="adds lpips, lpips-vgg, dists, niqe and clipiqa, and musiq"):
+    with pytest.raises(NotImplementedError, match="--metric_weights DIR adds") as e:
         cli.main(["--input_dir", str(tmp_path), "--eval_metrics", "musiq"])
+    added = re.split(r", | and ", str(e.value).split("--metric_weights DIR adds ")[1].rstrip(")"))
+    assert added == list(M.NETWORK_METRICS + M.NR_METRICS) and added[-1] == "musiq"     # every registered metric that needs weights, by name
