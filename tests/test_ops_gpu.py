@@ -131,8 +131,11 @@ LIN_CASES = [
     ("lin8_k64", 4100, 64, 256, {}),
     ("lin8_k96", 4200, 96, 128, {}),
     ("lin8_k128", 4608, 128, 3072, {}),
-    # gemm8p persistent 256x256 kernel (M >= 4096, cout % 256 == 0, cin % 128 == 0): ragged M tail, one and many K chunks,
-    # more tiles than CUs (tile switch inside a workgroup), GELU / gated in-place residual epilogues
+    # gemm8p persistent 256x256 kernel (M >= 4096, cout % 256 == 0, cin % 128 == 0): ragged M tail, one and many K chunks, GELU / gated
+    # in-place residual epilogues.  Since gemm_tail_split, lin4x_many_tiles is 316 tiles = a 256-tile main launch (exactly ONE tile per
+    # workgroup on 256 CUs) + an igemm_fast tail, and lin4x_many_tiles_gate is 237 tiles on 237 workgroups: neither switches tiles inside a
+    # workgroup.  Of this list only lin4x_tail_dit_out does (864 tiles -> 768 in three rounds + tail); the walk classes (tiles per workgroup,
+    # off-stream successors, supertile groups) are enumerated and pinned by tests/igemm_cases.py / tests/test_igemm_fp64_gpu.py
     ("lin4x_ragged", 4099, 256, 256, {}),
     ("lin4x_many_tiles", 20011, 256, 1024, {}),
     ("lin4x_many_tiles_gate", 20011, 384, 768, {"gate": True, "inplace": True}),
