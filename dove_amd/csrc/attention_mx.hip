@@ -28,11 +28,11 @@ typedef int v8i __attribute__((ext_vector_type(8)));
 
 namespace {
 __device__ __forceinline__ unsigned e8m0_amax(float amax) {      // smallest power of two s with amax / s <= 448 (mxfp8.hip)
-  if (!(amax > 0.f)) return 0u;
+  if (!(amax > 0x1.cp-119f)) return 0u;                           // amax <= 448 * 2^-127: the smallest scale, 2^-127, holds it
   const unsigned u = __float_as_uint(amax * (1.0f / 448.0f));
   int e = (int)((u >> 23) & 0xff);
   if (u & 0x7fffffu) e += 1;
-  return (unsigned)(e < 0 ? 0 : (e > 254 ? 254 : e));
+  return (unsigned)(e < 1 ? 1 : (e > 254 ? 254 : e));             // the product below 2^-126 is an fp32 subnormal: exponent field 0
 }
 __device__ __forceinline__ unsigned pack4_fp8(float a, float b, float c, float d) {
   unsigned r = 0;

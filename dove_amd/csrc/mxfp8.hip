@@ -6,8 +6,9 @@
 // only the block-scaled v_mfma_scale_f32_32x32x64_f8f6f4 runs above the bf16 MFMA rate (plain fp8 MFMA = bf16 rate), and
 // it applies both scales inside the matrix pipe - no dequantisation pass exists anywhere.
 //
-//   dove_mx_quant_bf16 : bf16 [R][K] -> e4m3 [R][K] + scales; per block s = 2^ceil(log2(amax / 448)) (nothing clips),
-//                        q = rne_e4m3(x / s).  Used for the weights once at load and for activations per call.
+//   dove_mx_quant_bf16 : bf16 [R][K] -> e4m3 [R][K] + scales; per block s = 2^ceil(log2(amax / 448)) (nothing clips), floored at
+//                        2^-127 (amax <= 448 * 2^-127, zero included), q = rne_e4m3(x / s).  Used for the weights once at load and for
+//                        activations per call.
 //   dove_linear_mxfp8  : out[M][N] (bf16) = epilogue( (xq * xs) (wq * ws)^T ), fp32 accumulation, the same fused
 //                        epilogue as the bf16 GEMM (bias, GELU(tanh), residual, AdaLN-Zero gate per row class).
 //
@@ -36,13 +37,13 @@ typedef int v8i __attribute__((ext_vector_type(8)));
 // quantiser: one thread = 8 consecutive elements (16 B in, 8 B out), 4 threads = one 32-element block
 // ------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ unsigned e8m0_for_amax(float amax) {
-  // smallest power of two s with amax / s <= 448 (e4m3fn max): s = 2^ceil(log2(amax / 448)); amax = 0 -> 2^-127
-  if (!(amax > 0.f)) return 0u;
+  // smallest power of two s in [2^-127, 2^127] with amax / s <= 448 (e4m3fn max): s = 2^ceil(log2(amax / 448)), floored at 2^-127
+  if (!(amax > 0x1.cp-119f)) return 0u;                  // amax <= 448 * 2^-127 (zero included): the smallest scale holds it
   const float r = amax * (1.0f / 448.0f);
   const unsigned u = __float_as_uint(r);
   int e = (int)((u >> 23) & 0xff);                       // biased exponent of r (floor(log2 r) + 127)
   if (u & 0x7fffffu) e += 1;                             // not an exact power of two: round the exponent up
-  if (e < 0) e = 0;
+  if (e < 1) e = 1;                                      // r below 2^-126 is an fp32 subnormal (field 0), or zero where they are flushed
   if (e > 254) e = 254;
   return (unsigned)e;
 }

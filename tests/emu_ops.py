@@ -345,8 +345,8 @@ def v8_store_order(x):
     return x[..., _v8_store_index(x.shape[-1])]
 
 
-def qkv_post_mx(qkv, N, Npad, heads, text_len, gq, bq, gk, bk, cos, sin, qscale, eps, Q8, K8, V8t, Vs):
-    """dove_qkv_post_mxfp8: same pre-processing, e4m3 outputs (uint8 views); V in MXFP8 along the keys (32-key blocks per d row)."""
+def qkv_post_mx_f32(qkv, N, Npad, heads, text_len, gq, bq, gk, bk, cos, sin, qscale, eps):
+    """The fp32 values dove_qkv_post_mxfp8 quantises: (Qf, Kf [heads][Npad][64], Vf [heads][64][Npad]), pad rows / keys zero."""
     Qf = torch.zeros(heads, Npad, 64)
     Kf = torch.zeros(heads, Npad, 64)
     Vf = torch.zeros(heads, 64, Npad)
@@ -366,6 +366,12 @@ def qkv_post_mx(qkv, N, Npad, heads, text_len, gq, bq, gk, bk, cos, sin, qscale,
     Qf[:, :N] = (q * (qscale * 8.0)).permute(1, 0, 2)
     Kf[:, :N] = k.permute(1, 0, 2)
     Vf[:, :, :N] = v.permute(1, 2, 0)
+    return Qf, Kf, Vf
+
+
+def qkv_post_mx(qkv, N, Npad, heads, text_len, gq, bq, gk, bk, cos, sin, qscale, eps, Q8, K8, V8t, Vs):
+    """dove_qkv_post_mxfp8: same pre-processing, e4m3 outputs (uint8 views); V in MXFP8 along the keys (32-key blocks per d row)."""
+    Qf, Kf, Vf = qkv_post_mx_f32(qkv, N, Npad, heads, text_len, gq, bq, gk, bk, cos, sin, qscale, eps)
     Q8.copy_(Qf.to(torch.float8_e4m3fn).view(torch.uint8))
     K8.copy_(Kf.to(torch.float8_e4m3fn).view(torch.uint8))
     vq, ve = mx_quant_ref(Vf.reshape(heads * 64, Npad))                  # blocks of 32 consecutive keys

@@ -6,7 +6,8 @@ families, against a float64 softmax of the same operand values:
     mx     attn_fwd_mx_kernel         (e4m3 operands)                     2 heads
 Per case: (a) closeness, (b) the kernel that ran, (c) nothing outside O written and every row of O written, (d) operand pads ignored
 bit for bit, (e) pipe2 == pipe1 bit for bit on the heads they share.  Then T5's attn_bias_kernel around its tile edges and
-dove_qkv_post_bf16 over the short lengths, head-group tails, text splits and both V^T packings."""
+dove_qkv_post_bf16 over the short lengths, head-group tails, text splits and both V^T packings, and dove_qkv_post_mxfp8 over the same
+lengths at rounding level (tests/mx_cases.py)."""
 import functools
 import math
 
@@ -215,6 +216,9 @@ def test_qkv_post_lengths(N, heads, text_len, packing, v_order):
                       1 + 0.1 * torch.randn(64, generator=g), 0.1 * torch.randn(64, generator=g))
     ang = torch.rand(max(N - text_len, 1), 32, generator=g) * 6.28
     cos, sin = ang.cos().repeat_interleave(2, 1).contiguous(), ang.sin().repeat_interleave(2, 1).contiguous()
+    if heads == 9:                                              # a table whose pair entries differ: cr[2i + 1] for cr[2i] is then visible
+        ang = torch.rand(max(N - text_len, 1), 64, generator=g) * 6.28
+        cos, sin = ang.cos().contiguous(), (ang + 0.3 * torch.randn(ang.shape, generator=g)).sin().contiguous()
     qscale = 0.125 * math.log2(math.e)
     z = lambda *s: torch.zeros(*s, dtype=BF)   # noqa: E731
     Qr, Kr, Vr = z(heads, npad, 64), z(heads, npad, 64), z(heads, 64, npad)
@@ -233,3 +237,49 @@ def test_qkv_post_lengths(N, heads, text_len, packing, v_order):
     assert torch.allclose(n2, want, rtol=1e-5, atol=0), (n2, want)
     for nm, flat, n in (("Qh", fq, Qg.numel()), ("Kh", fk, Kg.numel()), ("Vt", fv, Vg.numel()), ("norm2", fn, n2.numel())):
         assert _guards_intact(flat, n), f"{nm}: wrote outside the buffer"
+
+
+def _guarded_u8(shape, pad=256):
+    """A uint8 tensor of `shape` prefilled with 0x55 inside a flat buffer with `pad` guard bytes (0xA7) on either side."""
+    n = math.prod(shape)
+    flat = torch.full((n + 2 * pad,), 0xA7, dtype=torch.uint8, device="cuda")
+    flat[pad:pad + n] = 0x55
+    return flat, flat[pad:pad + n].view(*shape)
+
+
+QKV_MX_CASES = [(N, heads, tl, rope) for N in QKV_LENGTHS for heads in (1, 9) for tl in sorted({0, min(226, N), N}) for rope in (True, False)]
+
+
+@pytest.mark.parametrize("N,heads,text_len,rope", QKV_MX_CASES, ids=["-".join(map(str, c)) for c in QKV_MX_CASES])
+def test_qkv_post_mx_lengths(N, heads, text_len, rope):
+    """dove_qkv_post_mxfp8 over the same lengths (Npad = the next multiple of 128, all the entry point takes): V8t / Vs bit-exact against the
+    exact MX rule of tests/mx_cases.py in the stored quad order, pad keys and whole pad tiles zero bytes with scale byte 0; Q8 / K8 within
+    0.5 ulp_e4m3 + k 2^-24 mag of a float64 LayerNorm + RoPE + scale, pad rows zero; cos / sin tables whose pair entries differ, or none.
+    All four outputs are guarded views prefilled with 0x55: the guards stay and every byte of [heads][Npad] is rewritten."""
+    import mx_cases as MC
+    npad = A.npad(N)
+    qkv, aff, cos, sin = MC.qkv_operands(N, heads, text_len, rope)
+    qscale = 0.125 * math.log2(math.e)
+    Qr, mQ, Kr, mK = MC.qkv_ref64(qkv, N, heads, text_len, aff, cos, sin, qscale, 1e-6)
+    V8r, Vsr = MC.v_exact(qkv, N, npad, heads)
+    (fq, Q8), (fk, K8) = _guarded_u8((heads, npad, 64)), _guarded_u8((heads, npad, 64))
+    (fv, V8), (fs, Vs) = _guarded_u8((heads, 64, npad)), _guarded_u8((heads, npad // 64, 64, 2))
+    dev = lambda t: None if t is None else t.cuda()   # noqa: E731
+    ops.qkv_post_mx(qkv.cuda(), N, npad, heads, text_len, *(t.cuda() for t in aff), dev(cos), dev(sin), qscale, 1e-6, Q8, K8, V8, Vs)
+    torch.cuda.synchronize()
+    for nm, flat, t in (("Q8", fq, Q8), ("K8", fk, K8), ("V8t", fv, V8), ("Vs", fs, Vs)):
+        f = flat.cpu()
+        assert bool((f[:256] == 0xA7).all()) and bool((f[256 + t.numel():] == 0xA7).all()), f"{nm}: wrote outside the buffer"
+    assert torch.equal(V8.cpu(), V8r), "V8t differs from the exact rule"
+    assert torch.equal(Vs.cpu(), Vsr), "Vs differs from the exact rule"
+    assert not bool(V8[:, :, N:].any()) and not bool(Vs.cpu().reshape(heads, npad // 64, 64, 2).permute(0, 2, 1, 3).reshape(heads, 64, npad // 32)
+                                                     [:, :, (N + 31) // 32:].any()), "pad keys / pad blocks are not zero"
+    for nm, got8, ref, mag in (("Q8", Q8, Qr, mQ), ("K8", K8, Kr, mK)):
+        g = got8.cpu()
+        assert not bool(g[:, N:].any()), f"{nm}: pad rows are not zero"
+        got = g[:, :N].contiguous().view(torch.float8_e4m3fn).float().double()
+        assert bool(torch.isfinite(got).all()), f"{nm}: a byte was never written or is NaN"
+        err, tol = (got - ref).abs(), MC.qkv_budget(ref, mag)
+        bad = ~(err <= tol)
+        assert not bool(bad.any()), (f"{nm}: {int(bad.sum())}/{bad.numel()} over the budget, worst {float((err / tol).max()):.3g}x; needs k "
+                                     f"{float(((err - 0.5 * MC.ulp_e4m3(ref)).clamp_min(0) / (MC.EPS24 * mag)).max()):.1f}")

@@ -857,7 +857,7 @@ def test_mx_quant_bit_exact():
 
 @pytest.mark.parametrize("M,N,K,act,resid,gate", [
     (300, 256, 512, 0, False, False),           # one ragged row tile, two scale chunks
-    (1000, 768, 1024, 1, False, False),         # GELU epilogue, several tiles per workgroup
+    (1000, 768, 1024, 1, False, False),         # GELU epilogue, 12 tiles: one per workgroup (the hand-over classes: tests/mx_cases.py)
     (700, 512, 3072, 0, True, True),            # gated residual (attn1.to_out.0 / ff.net.2 epilogue), DiT K
     (513, 256, 12288, 0, True, False),          # deep K (ff.net.2), plain residual
 ])
