@@ -155,8 +155,7 @@ def _save_clip_y4m(out, video, pads, args, path, chroma, color_fix, need_frames)
     return prepost.load_frames(path, yuv_matrix=args.yuv_matrix) if need_frames else None
 
 
-def main(argv=None):
-    from . import eval_metrics
+def build_parser() -> argparse.ArgumentParser:
     from . import metrics as M
     ap = argparse.ArgumentParser(description="VSR using DOVE on MI355X (dove_amd)")
     ap.add_argument("--input_dir", type=str, required=True)
@@ -169,11 +168,18 @@ def main(argv=None):
                          "--gt_dir); the other network metrics of pyiqa are not provided")
     ap.add_argument("--metric_weights", type=str, default="", help=f"directory with the files of {M.weights_help()}")
     ap.add_argument("--png_save", action="store_true")
+    ap.add_argument("--png_encoder", type=str, default="pil", choices=("pil", "gpu"),
+                    help="who writes the --png_save files: PIL on the host, or the GPU encoder (dove_amd.png)")
     ap.add_argument("--y4m_save", action="store_true",
                     help="write <clip>.y4m (YUV4MPEG2) with --fps and --save_format; with --chunk_len > 0 it is streamed chunk by chunk")
     ap.add_argument("--eval_psnr_dir", type=str, default=None)
     add_model_arguments(ap)
-    args = ap.parse_args(argv)
+    return ap
+
+
+def main(argv=None):
+    from . import eval_metrics
+    args = build_parser().parse_args(argv)
     check_dtype(args)
     metrics = [m.strip().lower() for m in args.eval_metrics.split(",") if m.strip()]
     check_eval_metrics(metrics, args.metric_weights, bool(args.gt_dir or args.eval_psnr_dir))
@@ -246,7 +252,7 @@ def main(argv=None):
         if args.y4m_save:
             pass
         elif args.png_save:
-            prepost.save_frames_as_png(frames_out, os.path.join(args.output_path, stem))
+            prepost.save_frames_as_png(frames_out, os.path.join(args.output_path, stem), encoder=args.png_encoder)
         else:
             import numpy as np
             np.save(os.path.join(args.output_path, stem + ".npy"), frames_out.cpu().numpy())

@@ -106,13 +106,13 @@ def fix_clip(pred_u8: torch.Tensor, source_u8: torch.Tensor, mode: str) -> torch
     return color_fix(pred, up.permute(1, 0, 2, 3), mode, out_dtype=torch.uint8, style_affine=(0.5, 0.5))
 
 
-def save_sequence(frames_u8: torch.Tensor, like: str, out_root: str) -> str:
+def save_sequence(frames_u8: torch.Tensor, like: str, out_root: str, png_encoder: str = "pil") -> str:
     """Write the fixed frames in the form of the prediction at ``like``: a PNG folder, one image, an ``.npy`` clip or a ``.y4m`` file."""
     from . import prepost
     base = os.path.basename(like.rstrip(os.sep))
     path = os.path.join(out_root, base)
     if os.path.isdir(like):
-        prepost.save_frames_as_png(frames_u8, path)
+        prepost.save_frames_as_png(frames_u8, path, encoder=png_encoder)
     elif like.lower().endswith(".npy"):
         import numpy as np
         np.save(path, frames_u8.cpu().numpy())
@@ -126,11 +126,15 @@ def save_sequence(frames_u8: torch.Tensor, like: str, out_root: str) -> str:
     else:
         from PIL import Image
         path = os.path.splitext(path)[0] + ".png"
-        Image.fromarray(frames_u8[0].cpu().numpy()).save(path)
+        if png_encoder == "gpu":
+            from . import png
+            png.save_frames(frames_u8[:1], os.path.dirname(path) or ".", names=[os.path.basename(path)])
+        else:
+            Image.fromarray(frames_u8[0].cpu().numpy()).save(path)
     return path
 
 
-def process(pred_root: str, source_root: str, out_root: str, mode: str) -> list:
+def process(pred_root: str, source_root: str, out_root: str, mode: str, png_encoder: str = "pil") -> list:
     from .eval_metrics import load_sequence
     if mode not in MODES:
         raise ValueError(f"--mode must be one of {sorted(MODES)}, got {mode!r}")
@@ -146,22 +150,28 @@ def process(pred_root: str, source_root: str, out_root: str, mode: str) -> list:
             print(f"Skipping {name}: pred {tuple(pred.shape)} does not match source {tuple(src.shape)} (equal size or an integer "
                   "upscale factor, and the same frame count).")
             continue
-        path = save_sequence(fix_clip(pred, src, mode), pred_files[name], out_root)
+        path = save_sequence(fix_clip(pred, src, mode), pred_files[name], out_root, png_encoder)
         print(f"{name}: {mode} colour fix -> {path}")
         done.append(name)
     print(f"Processed {len(done)} samples.")
     return done
 
 
-def main(argv=None):
+def build_parser() -> argparse.ArgumentParser:
     parser = argparse.ArgumentParser(description="Colour fix (wavelet / AdaIN) of SR results against their source on the GPU (dove_amd)")
     parser.add_argument("--pred", type=str, required=True, help="folder of restored results (PNG folders, images, .npy clips)")
     parser.add_argument("--source", type=str, required=True, help="folder of the inputs they were restored from (same size, or smaller "
                         "by an integer factor: upscaled bilinearly first)")
     parser.add_argument("--out", type=str, required=True, help="folder the fixed results are written to")
     parser.add_argument("--mode", type=str, choices=sorted(MODES), default="wavelet")
-    args = parser.parse_args(argv)
-    return process(args.pred, args.source, args.out, args.mode)
+    parser.add_argument("--png_encoder", type=str, default="pil", choices=("pil", "gpu"),
+                        help="who writes PNG results: PIL on the host, or the GPU encoder (dove_amd.png)")
+    return parser
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    return process(args.pred, args.source, args.out, args.mode, args.png_encoder)
 
 
 if __name__ == "__main__":

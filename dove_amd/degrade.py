@@ -424,6 +424,9 @@ def degrade_clip(path, out_stem, args, recipe=None):
                     writer.write(yuv.rgb_to_yuv(lq, fmt).cpu())
                 elif mm is not None:
                     mm[f0:f0 + lq.shape[0]] = lq.cpu().numpy()
+                elif getattr(args, "png_encoder", "pil") == "gpu":
+                    from . import png
+                    png.save_frames(lq, out_stem, names=[f"{f0 + i:03d}.png" for i in range(lq.shape[0])])
                 else:
                     for i, fr in enumerate(lq.cpu().numpy()):
                         Image.fromarray(fr).save(os.path.join(out_stem, f"{f0 + i:03d}.png"))
@@ -439,7 +442,7 @@ def degrade_clip(path, out_stem, args, recipe=None):
     return recipe
 
 
-def main(argv=None):
+def build_parser():
     import argparse
     ap = argparse.ArgumentParser(description="Degrade ground-truth clips into low-quality ones on the GPU (dove_amd)")
     ap.add_argument("--input_dir", type=str, required=True, help="PNG folders, .npy arrays (uint8 [F,H,W,3]) and .y4m files")
@@ -450,13 +453,19 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--recipe_in", type=str, default=None, help="replay this recipe (.json) instead of drawing one")
     ap.add_argument("--png_save", action="store_true")
+    ap.add_argument("--png_encoder", type=str, default="pil", choices=("pil", "gpu"),
+                    help="who writes the --png_save files: PIL on the host, or the GPU encoder (dove_amd.png)")
     ap.add_argument("--y4m_save", action="store_true")
     ap.add_argument("--block", type=int, default=16, help="frames read, processed and written at a time")
     ap.add_argument("--fps", type=int, default=16)
     ap.add_argument("--save_format", type=str, default="yuv444p")
     ap.add_argument("--yuv_matrix", type=str, default="bt601", choices=("bt601", "bt709"))
     ap.add_argument("--yuv_range", type=str, default=None, choices=("limited", "full"))
-    args = ap.parse_args(argv)
+    return ap
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
     if args.y4m_save and args.png_save:
         raise ValueError("--y4m_save and --png_save: choose one output form")
     if sum(x is not None for x in (args.config, args.preset, args.recipe_in)) != 1:

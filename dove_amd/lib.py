@@ -267,6 +267,9 @@ SIGNATURES = {
     "dove_mha_f32": [_VP, _VP, _VP, _LL, _I, _I, _I, _F, _VP, _LL, _VP],
     "dove_gelu_f32": [_VP, _LL, _VP, _VP],
     "dove_musiq_score": [_VP, _LL, _VP, _VP, _I, _I, _I, _VP, _VP],
+    # PNG encoder (csrc/png.hip): whole files on the device, and its deflate stage on a plain buffer
+    "dove_png_encode": [C.POINTER(ImageView), _I, _I, _I, _I, _VP, C.c_size_t, _VP, _VP, _VP],
+    "dove_zlib_huffman": [_VP, _LL, _LL, _VP, C.c_size_t, _VP, _VP, _VP],
 }
 PLAIN = {"dove_last_error": (C.c_char_p, []), "dove_abi_version": (C.c_int, []), "dove_comm_destroy": (None, [C.c_void_p]),
          "dove_conv_gn_partial_rows": (C.c_longlong, [C.POINTER(ConvDesc)]),
@@ -298,7 +301,12 @@ PLAIN = {"dove_last_error": (C.c_char_p, []), "dove_abi_version": (C.c_int, []),
          "dove_niqe_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
          "dove_resnet_conv_f32_kernel_name": (C.c_char_p, [C.POINTER(ResnetConvF32Args)]),
          "dove_clip_attnpool_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
-         "dove_mha_f32_tiles": (None, [C.POINTER(C.c_int), C.POINTER(C.c_int)])}
+         "dove_mha_f32_tiles": (None, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+         "dove_png_segment_rows": (C.c_int, [_I, _I]),
+         "dove_png_bound": (C.c_size_t, [_I, _I, _I]),
+         "dove_png_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I]),
+         "dove_zlib_huffman_bound": (C.c_size_t, [_LL, _LL]),
+         "dove_zlib_huffman_workspace_bytes": (C.c_size_t, [_LL, _LL])}
 
 
 def kernel_source_sha256() -> str:

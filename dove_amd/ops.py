@@ -771,6 +771,52 @@ def yuv_to_rgb_u8(payload: torch.Tensor, h: int, w: int, fmt: L.YuvFormat) -> to
     return out
 
 
+def png_segment_rows(w: int, channels: int) -> int:
+    """Rows of one deflate segment of the PNG encoder (host function; 0 for a bad argument)."""
+    return int(L.load().dove_png_segment_rows(w, channels))
+
+
+def png_bound(h: int, w: int, channels: int) -> int:
+    """The most bytes one encoded h x w file can take (host function; 0 for a bad argument)."""
+    return int(L.load().dove_png_bound(h, w, channels))
+
+
+def png_encode(img: torch.Tensor):
+    """img: a [N,C,H,W] view, C in {1, 3} (any strides, no copy; uint8, or float32 / bfloat16 in [0,1]) -> (files uint8 [N, png_bound],
+    sizes int64 [N]) on the device: row i holds one complete PNG file in its first sizes[i] bytes (csrc/png.hip)."""
+    if img.dim() != 4 or img.shape[1] not in (1, 3):
+        raise ValueError(f"png_encode: img {tuple(img.shape)} must be a [N,1,H,W] or [N,3,H,W] view")
+    if not img.is_cuda:
+        raise RuntimeError("png_encode needs its input on the HIP device (`cuda`); there is no CPU path")
+    N, Cc, H, W = img.shape
+    lib = L.load()
+    with torch.cuda.device(img.device):
+        out = torch.empty(N, int(lib.dove_png_bound(H, W, Cc)), dtype=torch.uint8, device=img.device)
+        sizes = torch.empty(N, dtype=torch.int64, device=img.device)
+        if N:
+            ws = torch.empty(max(int(lib.dove_png_workspace_bytes(N, H, W, Cc)), 8), dtype=torch.uint8, device=img.device)
+            v = _image_view(img)
+            L.check(lib.dove_png_encode(C.byref(v), N, H, W, Cc, L.ptr(ws), ws.numel(), L.ptr(out), L.ptr(sizes), L.stream_ptr()),
+                    "dove_png_encode")
+    return out, sizes
+
+
+def zlib_huffman(data: torch.Tensor, segment_bytes: int = 32768):
+    """data: contiguous uint8 on the device -> (stream uint8 [bound], size int64 [1]) on the device: a zlib stream of literal-only
+    dynamic-Huffman blocks, one per ``segment_bytes`` of input (the PNG encoder's deflate stage; csrc/png.hip)."""
+    if data.dtype != torch.uint8 or data.dim() != 1:
+        raise ValueError(f"zlib_huffman: expected a 1-D uint8 tensor, got {tuple(data.shape)} {data.dtype}")
+    L.require_cuda(data)
+    lib = L.load()
+    n = data.numel()
+    out = torch.empty(max(int(lib.dove_zlib_huffman_bound(n, segment_bytes)), 8), dtype=torch.uint8, device=data.device)
+    ws = torch.empty(max(int(lib.dove_zlib_huffman_workspace_bytes(n, segment_bytes)), 8), dtype=torch.uint8, device=data.device)
+    size = torch.empty(1, dtype=torch.int64, device=data.device)
+    L.check(lib.dove_zlib_huffman(L.ptr(data), n, segment_bytes, L.ptr(ws), ws.numel(), L.ptr(out), L.ptr(size), L.stream_ptr()),
+            "dove_zlib_huffman")
+    return out, size
+
+
 def randn(shape, seed: int, stream_id: int = 0, dtype=torch.float32, offset: int = 0, device="cuda") -> torch.Tensor:
     """Standard normals of the library's counter-based generator (csrc/video.hip ``dove_randn``: Philox4x32-10 keyed by ``seed``, counter
     (element / 4, ``stream_id``), Box-Muller; tests/randn_ref.py is the definition): the elements [offset, offset + numel) of stream

@@ -106,8 +106,15 @@ def load_frames(path: str, yuv_matrix: str = "bt601", yuv_range: str | None = No
     return torch.from_numpy(arr.copy())
 
 
-def save_frames_as_png(frames_u8: torch.Tensor, output_dir: str):
-    """Same file naming as the reference's ``save_frames_as_png`` (ref :111-128)."""
+def save_frames_as_png(frames_u8: torch.Tensor, output_dir: str, encoder: str = "pil"):
+    """Same file naming as the reference's ``save_frames_as_png`` (ref :111-128).  ``encoder``: 'pil' (the default: PIL's writer on the
+    host) or 'gpu' (dove_amd.png: the files are encoded on the device and only written here)."""
+    if encoder == "gpu":
+        from . import png
+        png.save_frames(frames_u8, output_dir)
+        return
+    if encoder != "pil":
+        raise ValueError(f"encoder must be 'pil' or 'gpu', got {encoder!r}")
     from PIL import Image
     os.makedirs(output_dir, exist_ok=True)
     for i, fr in enumerate(frames_u8.cpu().numpy()):

@@ -886,6 +886,31 @@ void dove_mha_f32_tiles(int* q_tile, int* kv_tile);
 int dove_gelu_f32(const float* x, long long count, float* out, void* stream);
 int dove_musiq_score(const float* features, long long ld, const float* w, const float* b, int n, int dim, int k, double* out, void* stream);
 
+/* ---- PNG encoder (csrc/png.hip; tests/png_ref.py is the bit-exact definition of the filtered stream) ----
+ * png_encode: img is a strided [n,channels,h,w] view as above (channels 3 = RGB, 1 = grey; u8 as it is, f32 / bf16 quantised as
+ *   dove_postprocess_u8 does, trunc(clamp(255 x, 0, 255))).  Frame i becomes a complete 8-bit, non-interlaced PNG file at
+ *   out + i * dove_png_bound(h, w, channels), sizes[i] bytes long (sizes is on the device): signature, IHDR, IDAT chunks, IEND, every
+ *   CRC-32 and the Adler-32 computed on the device.  Each scanline takes the filter (None, Sub, Up, Average, Paeth) with the smallest sum
+ *   of |filtered byte read as int8|, ties to the lower id.  The filtered stream is cut into segments of dove_png_segment_rows(w, channels)
+ *   whole rows (ceil(32768 / (w channels + 1))); each segment is one literal-only dynamic-Huffman deflate block (code lengths <= 15 bits,
+ *   or the flat code - 255 symbols of 8 bits, 2 of 9 - where the built code would cost more payload bits) followed by an empty stored
+ *   block, in an IDAT chunk of its own.  No LZ77 matches: a file is never below 1/8 of its raw size.
+ *   dove_png_bound = filtered bytes * 9 / 8 + 256 per segment + 64, the most bytes a file can take (0 for a bad shape).
+ *   ws: device scratch of dove_png_workspace_bytes(n, h, w, channels) bytes, 8-byte aligned.  Integer arithmetic only: two calls give
+ *   identical bytes and a frame's file does not depend on the batch it is encoded in.
+ * zlib_huffman: the same deflate stage on nbytes >= 1 plain bytes in segments of segment_bytes (1 KiB .. 1 MiB): out receives one zlib
+ *   stream (header 78 01, the segments, a final empty block, Adler-32) of *size bytes (size is on the device), at most
+ *   dove_zlib_huffman_bound(nbytes, segment_bytes); ws: dove_zlib_huffman_workspace_bytes(nbytes, segment_bytes) bytes. */
+int dove_png_segment_rows(int w, int channels);
+size_t dove_png_bound(int h, int w, int channels);
+size_t dove_png_workspace_bytes(int n, int h, int w, int channels);
+int dove_png_encode(const dove_image_view* img, int n, int h, int w, int channels, void* ws, size_t ws_bytes, unsigned char* out,
+                    long long* sizes, void* stream);
+size_t dove_zlib_huffman_bound(long long nbytes, long long segment_bytes);
+size_t dove_zlib_huffman_workspace_bytes(long long nbytes, long long segment_bytes);
+int dove_zlib_huffman(const unsigned char* in, long long nbytes, long long segment_bytes, void* ws, size_t ws_bytes, unsigned char* out,
+                      long long* size, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
