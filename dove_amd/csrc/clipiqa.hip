@@ -1,28 +1,7 @@
 // CLIP-IQA (include/dove_hip.h has the contract): the operators of CLIP RN50's ModifiedResNet in exact fp32, the
-// attention-pool head and the prompt-pair score in fp64.  Activations are channels-last fp32 [n][h][w][c] with pixel strides, weights
-// [kh][kw][cin][cout] with BatchNorm folded in by the host, as in percep.hip.
+// attention-pool head and the prompt-pair score in fp64.  Activations are channels-last fp32 [n][h][w][c] with pixel strides, as in
+// percep.hip.  The tower's convolution (dove_resnet_conv_f32, pool-on-load and residual included) is in conv_f32.hip.
 //
-// dove_resnet_conv_f32 chooses one of four walks from the arguments alone (dove_resnet_conv_f32_kernel_name):
-//   pointwise_f32_kernel (new): k = 1, stride 1, cin % 32 == 0, cout % 4 == 0, ldx % 4 == 0, 16-byte aligned x and w.  A plain GEMM of M = n h w
-//     pixels on v_mfma_f32_32x32x2_f32.  One 256-thread block owns 128 pixels x TN channels, TN = 128 for cout >= 128 and 64 below; the four
-//     waves form a 2 x 2 grid of 64 x TN/2 quarters.  K advances 32 channels at a time through double-buffered LDS exactly as in
-//     convnet3x3_f32_kernel: the loads of step k + 1 are issued before the MFMAs of step k, one barrier per step.  K ascends in one fmaf
-//     chain per output, no split-K, so the bits do not depend on TN or on the tile an output falls in and equal conv_f32_kernel's.  With
-//     pool = 2 (the same body, MODE_POOL) the A loader keeps the four input pixels of an output pixel in flight and stages ((a + b) + (c + d)) * 0.25f: the conv of the 2 x 2
-//     average (floor sizes) without the pooled map ever being written.  Epilogue: (acc + bias) + residual, then ReLU.  residual may be out:
-//     each element is read and written by the same thread.
-//   convnet3x3_n64_f32_kernel (new): k = 3, stride 1, pad 1, cin % 32 == 0, cout in {32, 64}: the walk of convnet3x3_f32_kernel (tap-major K,
-//     one tap x 32 channels per step, a 9-bit tap mask per row) on the 128 x 64 tile, so no MFMA of the stem and stage-1 convs multiplies an
-//     empty half tile.  Same K order, same bits.
-//   convnet3x3_f32_kernel (percep.hip, called through its hidden launcher): k = 3, stride 1, cout >= 128.
-//   conv_f32_kernel (flow.hip): everything else, i.e. the 3 -> 32 stride-2 stem conv (K = 27) and a k = 1 conv whose cin is no multiple
-//     of 32.  It has neither a residual nor pool-on-load: those two are refused outside pointwise_f32_kernel.
-//   LDS banks of the two new walks (one body): fragments are read with ds_read_b32, bank = dword address mod 32 within a 32-lane half.
-//     A [128][33]: lane l of a half reads row r0 + l, column 2 s + half: dword 33 (r0 + l) + k, bank (const + l) mod 32: 32 different banks
-//       (an unpadded row of 32 would put all lanes on one).  B [32][TN]: lane l reads row 2 s + half, column c0 + l: consecutive dwords, 32
-//       different banks for TN = 64 as for 128, since a row is a multiple of 32 dwords and the lanes walk along it.
-//     A is filled with ds_write_b32: a half holds rows r .. r + 3 x 8 chunks q, dword 33 row + 4 q + e -> bank (const + (l >> 3) + 4 (l & 7))
-//       mod 32, all different.  B is filled with 16-byte writes of consecutive dwords.
 // avgpool_cl_kernel: one thread per output element, ((a + b) + (c + d)) * 0.25f in the order of pool-on-load.
 // Attention pool.  Only token 0 (the mean token) is a query, so K and V are never projected over the tokens.  With T the h w + 1 tokens,
 //   q = Wq T_0 + bq, per head u_h = Wk_h^T q_h and c_h = q_h . bk_h give the scores s_t,h = (T_t . u_h + c_h) / 8 = q_h . (Wk_h T_t + bk_h) / 8;
@@ -35,186 +14,15 @@
 #include "common.h"
 #include "../../include/dove_hip.h"
 
-int dove_conv_f32_general_launch(const float* x, const float* w, const float* bias, float* out, int n, int h, int w_in, int cin, int cout,
-                                 int kh, int kw, int stride, int pad_h, int pad_w, int relu, long long ldx, long long ldo, void* stream);
-int dove_convnet3x3_fast_launch(const float* x, const float* w, const float* bias, float* out, int n, int h, int w_in, int cin, int cout,
-                                int relu, long long ldx, long long ldo, void* stream);
-
 namespace {
 
 constexpr int NT = 256;
-constexpr int TM = 128, TK = 32, TLDA = TK + 1;
 constexpr int AP_SLICE = 256;                                       // tokens per attention-pool partial
 constexpr int AP_C = 2048, AP_HEADS = 32, AP_HD = 64, AP_OUT = 1024;
 constexpr int AP_TOK = 4;                                           // tokens per block of the score kernel
 constexpr long long MAX_ELEMS = (long long)NT * 0x7fffffffLL;
-const char* const POINTWISE_NAME = "pointwise_f32_kernel";
-const char* const N64_NAME = "convnet3x3_n64_f32_kernel";
-const char* const FAST_NAME = "convnet3x3_f32_kernel";
-const char* const GENERAL_NAME = "conv_f32_kernel";
 
 inline unsigned blocks_for(long long total) { return (unsigned)((total + NT - 1) / NT); }
-constexpr int tile_lds(int tn) { return 2 * (TM * TLDA + TK * tn) * (int)sizeof(float); }   // 66,560 bytes for 128, 50,176 for 64
-
-// ------------------------------------------------- the 128 x TN tile: 1 x 1, pooled 1 x 1, 3 x 3 -------------------------------------------------
-struct TileP {
-  const float* x; const float* w; const float* bias; const float* res; float* out;
-  int H, W, Cin, Cout, relu;                   // H, W: the output map (the pooled map under pool-on-load)
-  int Hi, Wi;                                  // MODE_POOL: the input map, H = Hi / 2, W = Wi / 2
-  long long M, ldx, ldr, ldo;
-};
-
-enum { MODE_1X1 = 0, MODE_POOL = 1, MODE_3X3 = 2 };
-
-template <int TN, int MODE>
-__device__ __forceinline__ void tile_body(const TileP& p) {
-  constexpr int F_A = TM * TLDA, F_B = TK * TN;
-  constexpr int BQ = TN / 4, BROWS = NT / BQ, NBJ = TK / BROWS;   // B loader: chunk bq of K rows br + BROWS j
-  constexpr int WN = TN / 2, NJ = WN / 32;                        // a wave's columns and accumulators across
-  constexpr int NP = MODE == MODE_POOL ? 4 : 1;                   // input pixels a row keeps in flight
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  float* const As = smem;                      // [2][TM][TLDA]
-  float* const Bs = smem + 2 * F_A;            // [2][TK][TN]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const long long m0 = (long long)blockIdx.x * TM;
-  const int n0 = blockIdx.y * TN;
-
-  // A loader: this thread reads the 16-byte chunk aq of rows ar + 32 j
-  const int aq = tid & 7, ar = tid >> 3;
-  const int bq = tid % BQ, br = tid / BQ;
-  long long poff[4];
-  unsigned vmask[4];                           // MODE_3X3: the valid taps; otherwise bit 0 = the row exists
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const long long m = m0 + ar + 32 * j;
-    poff[j] = 0;
-    vmask[j] = 0;
-    if (m < p.M) {
-      poff[j] = m * p.ldx + aq * 4;
-      vmask[j] = 1u;
-      if (MODE != MODE_1X1) {
-        const long long hw = (long long)p.H * p.W, img = m / hw;
-        const int r = (int)(m - img * hw), oy = r / p.W, ox = r - oy * p.W;
-        if (MODE == MODE_POOL) poff[j] = ((img * p.Hi + 2 * oy) * p.Wi + 2 * ox) * p.ldx + aq * 4;   // the upper left of the four
-        if (MODE == MODE_3X3) vmask[j] = 0;
-#pragma unroll
-        for (int t = 0; t < 9; ++t) {
-          const int iy = oy + t / 3 - 1, ix = ox + t % 3 - 1;
-          if (MODE == MODE_3X3 && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W) vmask[j] |= 1u << t;
-        }
-      }
-    }
-  }
-  const bool bvalid = n0 + bq * 4 < p.Cout;    // cout % 4 == 0: a chunk is inside or outside as a whole
-  const float* wp = p.w + (long long)br * p.Cout + n0 + bq * 4;
-
-  f32x16 acc[2][NJ];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-  const int wm = (wave >> 1) * 64, wn = (wave & 1) * WN, l31 = lane & 31, half = lane >> 5;
-
-  int tap = 0, kx = 0, ci = 0;
-  long long toff = MODE == MODE_3X3 ? -((long long)p.W + 1) * p.ldx : 0;
-  const long long wstep = (long long)TK * p.Cout, prow = (long long)p.Wi * p.ldx;
-  f32x4 av[4][NP], bv[NBJ];
-  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-
-  auto load = [&]() {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      if (MODE == MODE_3X3) {
-        av[j][0] = ((vmask[j] >> tap) & 1u) ? *(const f32x4*)(p.x + poff[j] + toff + ci) : zero4;
-      } else {
-        const float* s = p.x + poff[j] + ci;
-        av[j][0] = vmask[j] ? *(const f32x4*)s : zero4;
-        if constexpr (MODE == MODE_POOL) {     // the other three pixels of the 2 x 2 window stay in flight with it
-          av[j][1] = vmask[j] ? *(const f32x4*)(s + p.ldx) : zero4;
-          av[j][2] = vmask[j] ? *(const f32x4*)(s + prow) : zero4;
-          av[j][3] = vmask[j] ? *(const f32x4*)(s + prow + p.ldx) : zero4;
-        }
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < NBJ; ++j) bv[j] = bvalid ? *(const f32x4*)(wp + (long long)(BROWS * j) * p.Cout) : zero4;
-    wp += wstep;
-    ci += TK;
-    if (MODE == MODE_3X3 && ci == p.Cin) {
-      ci = 0;
-      ++tap;
-      toff += p.ldx;
-      if (++kx == 3) {
-        kx = 0;
-        toff += ((long long)p.W - 3) * p.ldx;
-      }
-    }
-  };
-  auto stage = [&](int buf) {
-    float* a = As + buf * F_A;
-    float* b = Bs + buf * F_B;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      float* d = a + (ar + 32 * j) * TLDA + aq * 4;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        if constexpr (MODE == MODE_POOL) d[e] = ((av[j][0][e] + av[j][1][e]) + (av[j][2][e] + av[j][3][e])) * 0.25f;
-        else d[e] = av[j][0][e];
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < NBJ; ++j) *(f32x4*)(b + (br + BROWS * j) * TN + bq * 4) = bv[j];
-  };
-
-  const int KT = (MODE == MODE_3X3 ? 9 : 1) * (p.Cin / TK);
-  load();
-  stage(0);
-  __syncthreads();
-  for (int kt = 0; kt < KT; ++kt) {
-    const int buf = kt & 1;
-    if (kt + 1 < KT) load();                   // in flight under this step's MFMAs
-    const float* a0 = As + buf * F_A + (wm + l31) * TLDA + half;
-    const float* a1 = a0 + 32 * TLDA;
-    const float* b0 = Bs + buf * F_B + half * TN + wn + l31;
-#pragma unroll
-    for (int s = 0; s < TK / 2; ++s) {
-      const float x0 = a0[2 * s], x1 = a1[2 * s];
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        const float y = b0[2 * s * TN + 32 * j];
-        acc[0][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(x0, y, acc[0][j], 0, 0, 0);
-        acc[1][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(x1, y, acc[1][j], 0, 0, 0);
-      }
-    }
-    if (kt + 1 < KT) stage(buf ^ 1);           // the other buffer: its readers finished before the barrier that ended step kt - 1
-    __syncthreads();
-  }
-
-#pragma unroll
-  for (int j = 0; j < NJ; ++j) {
-    const int n = n0 + wn + 32 * j + l31;
-    if (n >= p.Cout) continue;
-    const float b = p.bias ? p.bias[n] : 0.f;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const long long m = m0 + wm + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * half;
-        if (m >= p.M) continue;
-        float v = acc[i][j][r] + b;
-        if (p.res) v += p.res[m * p.ldr + n];
-        if (p.relu) v = fmaxf(v, 0.f);
-        p.out[m * p.ldo + n] = v;
-      }
-  }
-}
-
-template <int TN, int MODE>
-__global__ __launch_bounds__(NT) void pointwise_f32_kernel(TileP p) { tile_body<TN, MODE>(p); }
-
-__global__ __launch_bounds__(NT) void convnet3x3_n64_f32_kernel(TileP p) { tile_body<64, MODE_3X3>(p); }
 
 // ----------------------------------------------------------------- avgpool -----------------------------------------------------------------
 __global__ __launch_bounds__(NT) void avgpool_cl_kernel(const float* __restrict__ x, long long ldx, int h, int w, int c, int ho, int wo,
@@ -250,12 +58,6 @@ inline ApWs ap_layout(long long HW) {
   l.o = l.pv + (long long)AP_HEADS * AP_C;
   l.total = l.o + AP_C;
   return l;
-}
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
 }
 
 // grid (S, 2048 / NT, n): the sum of a slice's tokens per channel
@@ -441,95 +243,11 @@ __global__ __launch_bounds__(NT) void clipiqa_score_kernel(const float* __restri
   if (tid == 0) out[n] = tot / (double)pairs;
 }
 
-// ------------------------------------------------------------- conv dispatch -------------------------------------------------------------
-enum Walk { WALK_REFUSED = 0, WALK_POINTWISE, WALK_N64, WALK_FAST, WALK_GENERAL };
-
-Walk conv_walk(const dove_resnet_conv_f32_args* a, bool report) {
-#define REFUSE(cond, ...)                        \
-  do {                                           \
-    if (!(cond)) {                               \
-      if (report) dove_set_error(__VA_ARGS__);   \
-      return WALK_REFUSED;                       \
-    }                                            \
-  } while (0)
-  REFUSE(a && a->struct_size == sizeof(dove_resnet_conv_f32_args), "dove_resnet_conv_f32: struct_size %u is not the library's %zu",
-         a ? a->struct_size : 0u, sizeof(dove_resnet_conv_f32_args));
-  REFUSE(a->x && a->w && a->out, "dove_resnet_conv_f32: null x / w / out");
-  REFUSE(a->n > 0 && a->h > 0 && a->w_in > 0 && a->cin > 0 && a->cout > 0, "dove_resnet_conv_f32: n, h, w, cin, cout must be positive");
-  REFUSE(a->k == 1 || a->k == 3, "dove_resnet_conv_f32: kernel side %d (1 or 3)", a->k);
-  REFUSE(a->stride == 1 || a->stride == 2, "dove_resnet_conv_f32: stride %d (1 or 2)", a->stride);
-  REFUSE(a->pool == 1 || a->pool == 2, "dove_resnet_conv_f32: pool %d (1 or 2)", a->pool);
-  REFUSE(a->pool == 1 || (a->k == 1 && a->stride == 1), "dove_resnet_conv_f32: pool 2 belongs to a 1 x 1 conv of stride 1 (k %d, stride %d)", a->k,
-         a->stride);
-  REFUSE(a->pool == 1 || (a->h >= 2 && a->w_in >= 2), "dove_resnet_conv_f32: image %d x %d is smaller than the 2 x 2 pool", a->h, a->w_in);
-  REFUSE(a->ldx >= a->cin && a->ldo >= a->cout && (!a->residual || a->ldr >= a->cout),
-         "dove_resnet_conv_f32: ldx %lld < cin %d, ldo %lld or ldr %lld < cout %d", a->ldx, a->cin, a->ldo, a->ldr, a->cout);
-  REFUSE((long long)a->n * a->h * a->w_in <= 0x7fffffffLL * 32 && (long long)a->n * a->h * a->w_in * a->ldx < (1LL << 46) &&
-             (long long)a->k * a->k * a->cin < (1 << 24),
-         "dove_resnet_conv_f32: problem too large");
-  const bool vec = a->cin % TK == 0 && a->cout % 4 == 0 && a->ldx % 4 == 0 && ((uintptr_t)a->x & 15) == 0 && ((uintptr_t)a->w & 15) == 0;
-  if (a->k == 1 && a->stride == 1 && vec) return WALK_POINTWISE;
-  REFUSE(a->pool == 1 && !a->residual,
-         "dove_resnet_conv_f32: pool 2 and a residual need pointwise_f32_kernel (k 1, stride 1, cin %% 32 == 0, cout %% 4 == 0, ldx %% 4 == 0, "
-         "16-byte aligned x and w); got k %d, stride %d, cin %d, cout %d, ldx %lld", a->k, a->stride, a->cin, a->cout, a->ldx);
-#undef REFUSE
-  if (a->k == 3 && a->stride == 1 && vec) {
-    if (a->cout == 32 || a->cout == 64) return WALK_N64;
-    if (a->cout >= 128) return WALK_FAST;
-  }
-  return WALK_GENERAL;
-}
-
-template <typename K>
-void launch_tile(K kernel, PerDeviceOnce& once, int tn, long long M, int cout, const TileP& p, void* stream) {
-  if (auto once_ = once.guard()) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, tile_lds(tn));
-  dim3 grid((unsigned)((M + TM - 1) / TM), (unsigned)((cout + tn - 1) / tn), 1);
-  hipLaunchKernelGGL(kernel, grid, dim3(NT), tile_lds(tn), (hipStream_t)stream, p);
-}
-
 size_t ap_ws_bytes(int n, int h, int w) { return (size_t)n * (size_t)ap_layout((long long)h * w).total * sizeof(double); }
 
 }  // namespace
 
 // ------------------------------------------------------------- C entries -------------------------------------------------------------
-extern "C" const char* dove_resnet_conv_f32_kernel_name(const dove_resnet_conv_f32_args* a) {
-  switch (conv_walk(a, false)) {
-    case WALK_POINTWISE: return POINTWISE_NAME;
-    case WALK_N64: return N64_NAME;
-    case WALK_FAST: return FAST_NAME;
-    case WALK_GENERAL: return GENERAL_NAME;
-    default: return "";
-  }
-}
-
-extern "C" int dove_resnet_conv_f32(const dove_resnet_conv_f32_args* a, void* stream) {
-  const Walk walk = conv_walk(a, true);
-  if (walk == WALK_REFUSED) return DOVE_EINVAL;
-  const int pad = a->k / 2;
-  if (walk == WALK_GENERAL)
-    return dove_conv_f32_general_launch(a->x, a->w, a->bias, a->out, a->n, a->h, a->w_in, a->cin, a->cout, a->k, a->k, a->stride, pad, pad,
-                                        a->relu, a->ldx, a->ldo, stream);
-  if (walk == WALK_FAST)
-    return dove_convnet3x3_fast_launch(a->x, a->w, a->bias, a->out, a->n, a->h, a->w_in, a->cin, a->cout, a->relu, a->ldx, a->ldo, stream);
-  TileP p;
-  p.x = a->x; p.w = a->w; p.bias = a->bias; p.res = a->residual; p.out = a->out;
-  p.H = a->h / a->pool; p.W = a->w_in / a->pool; p.Cin = a->cin; p.Cout = a->cout; p.relu = a->relu;
-  p.Hi = a->h; p.Wi = a->w_in;
-  p.M = (long long)a->n * p.H * p.W; p.ldx = a->ldx; p.ldr = a->ldr; p.ldo = a->ldo;
-  static PerDeviceOnce once[5];
-  if (walk == WALK_N64) {
-    launch_tile(convnet3x3_n64_f32_kernel, once[0], 64, p.M, a->cout, p, stream);
-  } else if (a->pool == 2) {
-    if (a->cout >= 128) launch_tile(pointwise_f32_kernel<128, MODE_POOL>, once[1], 128, p.M, a->cout, p, stream);
-    else launch_tile(pointwise_f32_kernel<64, MODE_POOL>, once[2], 64, p.M, a->cout, p, stream);
-  } else {
-    if (a->cout >= 128) launch_tile(pointwise_f32_kernel<128, MODE_1X1>, once[3], 128, p.M, a->cout, p, stream);
-    else launch_tile(pointwise_f32_kernel<64, MODE_1X1>, once[4], 64, p.M, a->cout, p, stream);
-  }
-  DOVE_CHECK_LAUNCH("dove_resnet_conv_f32");
-  return DOVE_OK;
-}
-
 extern "C" int dove_avgpool_cl_f32(const float* x, long long ldx, int n, int h, int w, int c, float* out, long long ldo, void* stream) {
   DOVE_CHECK_ARG(x && out, "dove_avgpool_cl_f32: null x / out");
   DOVE_CHECK_ARG(n > 0 && h >= 2 && w >= 2 && c > 0, "dove_avgpool_cl_f32: n, c must be positive and h, w at least 2");

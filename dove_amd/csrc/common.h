@@ -104,6 +104,12 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
 // x * sigmoid(x) with the hardware reciprocal (1 ulp): an IEEE fp32 division is ~10 VALU instructions per element, and the result
 // is rounded to bf16 right after
 __device__ __forceinline__ float silu_f(float x) {

@@ -1,12 +1,7 @@
 // Optical flow (RAFT) and the warping error, all in fp32 (include/dove_hip.h has the contract).  Activations are
-// channels-last fp32: [n][h][w][c] with a pixel stride that may exceed c, so producers fill slices of a concat buffer.
+// channels-last fp32: [n][h][w][c] with a pixel stride that may exceed c, so producers fill slices of a concat buffer.  The convolutions and
+// the all-pairs correlation are in conv_f32.hip.
 //
-// conv2d_f32: implicit GEMM on v_mfma_f32_32x32x2_f32, M = n * ho * wo output pixels, N = cout, K = kh * kw * cin ordered tap-major then
-//   channel.  One 256-thread block owns a 64 x 64 tile; K advances 32 at a time through LDS (A [64][33], B [32][96]: both fragment reads
-//   are conflict-free); each of the four waves owns one 32 x 32 accumulator.  Every output is one k-ordered fmaf chain whatever the tile
-//   it falls in and whatever the batch: there is no split-K, so the bits do not depend on the launch geometry.  All of M, N and K are
-//   ragged: out-of-range elements are loaded as zeros and never stored.  The same kernel computes the all-pairs correlation (a 1 x 1
-//   conv whose weights are the second feature map, read transposed, with blockIdx.z as the pair).
 // instance_norm_f32: slices of 256 pixels give (mean, M2) partials by a local two-pass sum in fp64; one thread per (n, c) merges them in
 //   slice order (Chan's update); a third launch applies.  No atomics: two calls give identical bits.
 // corr_lookup, gru glue, convex upsampling: one thread per output element.
@@ -17,122 +12,8 @@
 namespace {
 
 constexpr int NT = 256;
-constexpr int BM = 64, BN = 64, BK = 32, LDA = BK + 1, LDB = BN + 32;
 constexpr int IN_SLICE = 256;             // pixels per instance-norm partial
 constexpr int LOOKUP_CH = 4 * 81;
-
-// ------------------------------------------------------------ conv2d_f32 ------------------------------------------------------------
-struct ConvP {
-  const float* x; const float* w; const float* bias; const float* scale; const float* shift; float* out;
-  int H, W, Cin, Ho, Wo, Cout, kw, stride, ph, pw, act, K;
-  long long M, ldx, ldo, ldwk, ldwn, bx, bw, bo;
-  float mul;
-};
-
-__device__ __forceinline__ float activate(float v, int act) {
-  if (act == DOVE_ACT_RELU) return fmaxf(v, 0.f);
-  // sigmoid and tanh in fp64: their own rounding stays below the accumulated error of the sum that feeds them
-  if (act == DOVE_ACT_SIGMOID) return (float)(1.0 / (1.0 + exp(-(double)v)));
-  if (act == DOVE_ACT_TANH) return (float)tanh((double)v);
-  return v;
-}
-
-template <bool WT>
-__global__ __launch_bounds__(NT) void conv_f32_kernel(ConvP p) {
-  __shared__ float As[BM * LDA];
-  __shared__ float Bs[BK * LDB];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const long long m0 = (long long)blockIdx.x * BM;
-  const int n0 = blockIdx.y * BN;
-  const float* x = p.x + blockIdx.z * p.bx;
-  const float* w = p.w + blockIdx.z * p.bw;
-  float* out = p.out + blockIdx.z * p.bo;
-
-  // A loader: this thread fills column ak of rows ar + 8 j
-  const int ak = tid & 31, ar = tid >> 5;
-  long long pbase[8];
-  int iy0[8], ix0[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const long long m = m0 + ar + 8 * j;
-    if (m < p.M) {
-      const long long img = m / ((long long)p.Ho * p.Wo);
-      const int r = (int)(m - img * p.Ho * p.Wo), oy = r / p.Wo, ox = r - oy * p.Wo;
-      pbase[j] = img * p.H * p.W;
-      iy0[j] = oy * p.stride - p.ph;
-      ix0[j] = ox * p.stride - p.pw;
-    } else {
-      pbase[j] = 0;
-      iy0[j] = -(1 << 28);                     // every tap of a row past M falls outside the image
-      ix0[j] = 0;
-    }
-  }
-  f32x16 acc;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-  const int wm = (wave >> 1) * 32, wn = (wave & 1) * 32;
-
-  for (int k0 = 0; k0 < p.K; k0 += BK) {
-    float av[8], bv[8];
-    {
-      const int k = k0 + ak;
-      const bool kv = k < p.K;
-      const int tap = kv ? k / p.Cin : 0, ci = k - tap * p.Cin, ky = tap / p.kw, kx = tap - ky * p.kw;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int iy = iy0[j] + ky, ix = ix0[j] + kx;
-        const bool ok = kv && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
-        av[j] = ok ? x[(pbase[j] + (long long)iy * p.W + ix) * p.ldx + ci] : 0.f;
-      }
-    }
-    if (!WT) {                                 // weights [K][cout]: lanes along cout
-      const int bn = tid & 63, bk = tid >> 6;
-      const bool nv = n0 + bn < p.Cout;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int k = k0 + bk + 4 * j;
-        bv[j] = (nv && k < p.K) ? w[(long long)k * p.ldwk + (long long)(n0 + bn) * p.ldwn] : 0.f;
-      }
-    } else {                                   // "weights" [cout][K] (the second feature map): lanes along K
-      const bool kv = k0 + ak < p.K;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int n = n0 + ar + 8 * j;
-        bv[j] = (kv && n < p.Cout) ? w[(long long)(k0 + ak) * p.ldwk + (long long)n * p.ldwn] : 0.f;
-      }
-    }
-    __syncthreads();                           // the previous tile's fragment reads are done
-#pragma unroll
-    for (int j = 0; j < 8; ++j) As[(ar + 8 * j) * LDA + ak] = av[j];
-    if (!WT) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) Bs[((tid >> 6) + 4 * j) * LDB + (tid & 63)] = bv[j];
-    } else {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) Bs[ak * LDB + ar + 8 * j] = bv[j];
-    }
-    __syncthreads();
-    const float* ap = As + (wm + (lane & 31)) * LDA + (lane >> 5);
-    const float* bp = Bs + (lane >> 5) * LDB + wn + (lane & 31);
-#pragma unroll
-    for (int s = 0; s < BK / 2; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ap[2 * s], bp[2 * s * LDB], acc, 0, 0, 0);
-  }
-
-  const int n = n0 + wn + (lane & 31);
-  if (n >= p.Cout) return;
-  const float b = p.bias ? p.bias[n] : 0.f;
-  const float sc = p.scale ? p.scale[n] : 1.f, sh = p.scale ? p.shift[n] : 0.f;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const long long m = m0 + wm + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-    if (m >= p.M) continue;
-    float v = acc[r] + b;
-    if (p.scale) v = fmaf(v, sc, sh);
-    v = activate(v, p.act);
-    if (p.mul != 1.f) v *= p.mul;
-    out[m * p.ldo + n] = v;
-  }
-}
 
 // ----------------------------------------------------------- instance norm -----------------------------------------------------------
 // block = 8 pixel rows x 32 channels; partial (mean, M2) of slice s of plane (n, c) at ws[((n C + c) S + s) 2]
@@ -425,61 +306,6 @@ constexpr long long MAX_ELEMS = (long long)NT * 0x7fffffffLL;      // one-dimens
 }  // namespace
 
 // ------------------------------------------------------------- C entries -------------------------------------------------------------
-extern "C" int dove_conv2d_f32(const dove_conv2d_f32_args* a, void* stream) {
-  DOVE_CHECK_ARG(a && a->struct_size == sizeof(dove_conv2d_f32_args), "dove_conv2d_f32: struct_size %u is not the library's %zu",
-                 a ? a->struct_size : 0u, sizeof(dove_conv2d_f32_args));
-  DOVE_CHECK_ARG(a->x && a->w && a->out, "dove_conv2d_f32: null x / w / out");
-  DOVE_CHECK_ARG(a->n > 0 && a->h > 0 && a->w_in > 0 && a->cin > 0 && a->cout > 0, "dove_conv2d_f32: n, h, w, cin, cout must be positive");
-  DOVE_CHECK_ARG((a->kh == 1 || a->kh == 3 || a->kh == 5 || a->kh == 7) && (a->kw == 1 || a->kw == 3 || a->kw == 5 || a->kw == 7),
-                 "dove_conv2d_f32: kernel %d x %d (sides are 1, 3, 5 or 7)", a->kh, a->kw);
-  DOVE_CHECK_ARG(a->stride == 1 || a->stride == 2, "dove_conv2d_f32: stride %d (1 or 2)", a->stride);
-  DOVE_CHECK_ARG(a->act >= DOVE_ACT_NONE && a->act <= DOVE_ACT_TANH, "dove_conv2d_f32: act %d", a->act);
-  DOVE_CHECK_ARG((a->scale == nullptr) == (a->shift == nullptr), "dove_conv2d_f32: scale and shift come together");
-  DOVE_CHECK_ARG(a->ldx >= a->cin && a->ldo >= a->cout, "dove_conv2d_f32: ldx %lld < cin %d or ldo %lld < cout %d", a->ldx, a->cin, a->ldo,
-                 a->cout);
-  ConvP p;
-  p.x = a->x; p.w = a->w; p.bias = a->bias; p.scale = a->scale; p.shift = a->shift; p.out = a->out;
-  p.H = a->h; p.W = a->w_in; p.Cin = a->cin; p.Cout = a->cout; p.kw = a->kw; p.stride = a->stride; p.act = a->act;
-  p.ph = a->kh / 2; p.pw = a->kw / 2;
-  p.Ho = (a->h + 2 * p.ph - a->kh) / a->stride + 1;
-  p.Wo = (a->w_in + 2 * p.pw - a->kw) / a->stride + 1;
-  p.M = (long long)a->n * p.Ho * p.Wo;
-  const long long K = (long long)a->kh * a->kw * a->cin;
-  DOVE_CHECK_ARG(p.M <= 0x7fffffffLL * BM / 2 && (long long)a->n * a->h * a->w_in < (1LL << 40) && K < (1 << 24),
-                 "dove_conv2d_f32: problem too large");
-  p.K = (int)K;
-  p.ldx = a->ldx; p.ldo = a->ldo; p.ldwk = a->cout; p.ldwn = 1; p.bx = p.bw = p.bo = 0;
-  p.mul = a->out_mul;
-  dim3 grid((unsigned)((p.M + BM - 1) / BM), (unsigned)((a->cout + BN - 1) / BN), 1);
-  hipLaunchKernelGGL(conv_f32_kernel<false>, grid, dim3(NT), 0, (hipStream_t)stream, p);
-  DOVE_CHECK_LAUNCH("dove_conv2d_f32");
-  return DOVE_OK;
-}
-
-// The general walk of dove_convnet_conv_f32 (percep.hip checks the arguments): conv_f32_kernel with the caller's padding and stride.
-__attribute__((visibility("hidden"))) int dove_conv_f32_general_launch(const float* x, const float* w, const float* bias, float* out, int n,
-                                                                       int h, int w_in, int cin, int cout, int kh, int kw, int stride,
-                                                                       int pad_h, int pad_w, int relu, long long ldx, long long ldo,
-                                                                       void* stream) {
-  ConvP p;
-  p.x = x; p.w = w; p.bias = bias; p.scale = p.shift = nullptr; p.out = out;
-  p.H = h; p.W = w_in; p.Cin = cin; p.Cout = cout; p.kw = kw; p.stride = stride; p.act = relu ? DOVE_ACT_RELU : DOVE_ACT_NONE;
-  p.ph = pad_h; p.pw = pad_w;
-  p.Ho = (h + 2 * pad_h - kh) / stride + 1;
-  p.Wo = (w_in + 2 * pad_w - kw) / stride + 1;
-  p.M = (long long)n * p.Ho * p.Wo;
-  const long long K = (long long)kh * kw * cin;
-  DOVE_CHECK_ARG(p.M <= 0x7fffffffLL * BM / 2 && (long long)n * h * w_in < (1LL << 40) && K < (1 << 24),
-                 "dove_convnet_conv_f32: problem too large");
-  p.K = (int)K;
-  p.ldx = ldx; p.ldo = ldo; p.ldwk = cout; p.ldwn = 1; p.bx = p.bw = p.bo = 0;
-  p.mul = 1.f;
-  dim3 grid((unsigned)((p.M + BM - 1) / BM), (unsigned)((cout + BN - 1) / BN), 1);
-  hipLaunchKernelGGL(conv_f32_kernel<false>, grid, dim3(NT), 0, (hipStream_t)stream, p);
-  DOVE_CHECK_LAUNCH("dove_convnet_conv_f32");
-  return DOVE_OK;
-}
-
 static size_t inorm_ws(int n, int h, int w, int c) {
   const long long S = ((long long)h * w + IN_SLICE - 1) / IN_SLICE;
   return (size_t)((long long)n * c * S * 2 * sizeof(double) + (long long)n * c * 2 * sizeof(float));
@@ -505,24 +331,6 @@ extern "C" int dove_instance_norm_f32(const float* x, int n, int h, int w, int c
   const long long total = (long long)n * HW * c;
   hipLaunchKernelGGL(inorm_apply_kernel, dim3(blocks_for(total)), dim3(NT), 0, (hipStream_t)stream, x, stats, resid, relu, HW, c, total, out);
   DOVE_CHECK_LAUNCH("dove_instance_norm_f32");
-  return DOVE_OK;
-}
-
-extern "C" int dove_corr_volume_f32(const float* fmap1, const float* fmap2, int n, int h, int w, int c, float scale, float* out,
-                                    void* stream) {
-  DOVE_CHECK_ARG(fmap1 && fmap2 && out, "dove_corr_volume_f32: null fmap1 / fmap2 / out");
-  DOVE_CHECK_ARG(n > 0 && n <= 65535 && h > 0 && w > 0 && c > 0 && (long long)h * w < (1 << 24),
-                 "dove_corr_volume_f32: n (<= 65535), h, w, c must be positive and h * w below 2^24");
-  const long long hw = (long long)h * w;
-  ConvP p;
-  p.x = fmap1; p.w = fmap2; p.bias = p.scale = p.shift = nullptr; p.out = out;
-  p.H = 1; p.W = (int)hw; p.Cin = c; p.Cout = (int)hw; p.kw = 1; p.stride = 1; p.act = DOVE_ACT_NONE; p.ph = p.pw = 0;
-  p.Ho = 1; p.Wo = (int)hw; p.M = hw; p.K = c;
-  p.ldx = c; p.ldo = hw; p.ldwk = 1; p.ldwn = c; p.bx = p.bw = hw * c; p.bo = hw * hw;
-  p.mul = scale;
-  dim3 grid((unsigned)((hw + BM - 1) / BM), (unsigned)((hw + BN - 1) / BN), n);
-  hipLaunchKernelGGL(conv_f32_kernel<true>, grid, dim3(NT), 0, (hipStream_t)stream, p);
-  DOVE_CHECK_LAUNCH("dove_corr_volume_f32");
   return DOVE_OK;
 }
 

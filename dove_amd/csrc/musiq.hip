@@ -1,5 +1,5 @@
 // MUSIQ (include/dove_hip.h has the contract): the operators of pyiqa's `musiq` that the fp32 metric block did not have.
-// The convs and Linears of the network run on dove_resnet_conv_f32 (clipiqa.hip: the 1 x 1 walk is the fp32 MFMA GEMM, tokens as pixels)
+// The convs and Linears of the network run on dove_resnet_conv_f32 (conv_f32.hip: the 1 x 1 walk is the fp32 MFMA GEMM, tokens as pixels)
 // and dove_convnet_conv_f32 (the 7 x 7 stem conv on conv_f32_kernel, over the explicitly padded frame that the gather writes); this file
 // adds what sits between them.  Activations are channels-last fp32; no atomics; repeated calls give identical bits; a frame's values do
 // not depend on the batch it is in (every sum below belongs to one patch, one token row or one query row).
@@ -203,12 +203,6 @@ __global__ __launch_bounds__(NT) void musiq_groupnorm_kernel(const float* __rest
 }
 
 // ------------------------------------------------------------------ LayerNorm ------------------------------------------------------------------
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 __global__ __launch_bounds__(NT) void layernorm_f32_kernel(const float* __restrict__ x, long long ldx, long long rows, int dim,
                                                            const float* __restrict__ gamma, const float* __restrict__ beta, double eps,
                                                            float* __restrict__ out, long long ldo) {

@@ -1,20 +1,7 @@
 // Perceptual metrics LPIPS and DISTS (include/dove_hip.h has the contract): the operators of a VGG16 / AlexNet trunk in
 // exact fp32 and the two statistical heads in fp64.  Activations are channels-last fp32 [n][h][w][c] with pixel strides, as in flow.hip.
+// The trunk's convolution (dove_convnet_conv_f32) is in conv_f32.hip.
 //
-// convnet3x3_f32_kernel: the 3 x 3, stride 1, pad 1 convs with cin % 32 == 0 and cout >= 128 as an implicit GEMM on v_mfma_f32_32x32x2_f32.  One 256-thread
-//   block owns 128 output pixels x 128 output channels; each of the four waves owns a 64 x 64 quarter as 2 x 2 accumulators.  K advances 32 at
-//   a time = one tap x 32 channels, so an A row is one contiguous 128-byte run of the input, read with 16-byte loads; the row's pixel offset
-//   and its 9-bit tap-validity mask are computed once, and the tap and channel counters advance by additions (no division in the loop).  LDS is
-//   double-buffered: the global loads of step k + 1 are issued before the MFMAs of step k and land in the other buffer after them, with one
-//   barrier per step.  K order is tap-major then channel ascending, every output is one fmaf chain whatever its tile (no split-K), the bias is
-//   added after the chain and the ReLU last: the bits are those of flow.hip's conv_f32_kernel.  M and N are ragged: zeros are loaded and
-//   nothing is stored outside.
-//   LDS banks: fragments are read with ds_read_b32, whose bank is (dword address) mod 32 within each 32-lane half.
-//     A [128][33]: lane l of a half reads row r0 + l, column 2 s + half: dword (r0 + l) * 33 + k = 33 r0 + k + 32 l + l, bank (const + l) mod 32:
-//       32 different banks.  Without the pad column the stride would be 32 and all 32 lanes would fall on one bank.
-//     B [32][128]: lane l of a half reads row 2 s + half, column c0 + l: consecutive dwords, 32 different banks; no pad is needed.
-//     A is filled with ds_write_b32 (bank mod 32 per half): a half holds 4 rows r..r+3 x 8 chunks q, dword row * 33 + 4 q + e -> bank
-//       (const + (l >> 3) + 4 (l & 7)) mod 32, again all different.  B is filled with 16-byte writes of consecutive dwords.
 // prep, maxpool, l2pool: one thread per output element.
 // lpips_layer: 16 lanes per pixel stride over the channels and reduce by a fixed butterfly; a block sums its 128 pixels in a fixed tree and
 //   writes one fp64 partial; a second launch sums the partials of an image in a fixed tree and adds the mean into out[n].
@@ -23,149 +10,14 @@
 #include "common.h"
 #include "../../include/dove_hip.h"
 
-int dove_conv_f32_general_launch(const float* x, const float* w, const float* bias, float* out, int n, int h, int w_in, int cin, int cout,
-                                 int kh, int kw, int stride, int pad_h, int pad_w, int relu, long long ldx, long long ldo, void* stream);
-int dove_convnet3x3_fast_launch(const float* x, const float* w, const float* bias, float* out, int n, int h, int w_in, int cin, int cout,
-                                int relu, long long ldx, long long ldo, void* stream);
-
 namespace {
 
 constexpr int NT = 256;
-constexpr int FM = 128, FN = 128, FK = 32, FLDA = FK + 1, FLDB = FN;
-constexpr int F_A = FM * FLDA, F_B = FK * FLDB;                     // floats per buffer
-constexpr int F_LDS = 2 * (F_A + F_B) * (int)sizeof(float);         // 66,560 bytes: above the static limit, so dynamic
 constexpr int LP_PIX = 128;                                         // pixels per lpips partial
 constexpr int DS_SLICE = 1024;                                      // pixels per dists partial
 constexpr long long MAX_ELEMS = (long long)NT * 0x7fffffffLL;
-const char* const FAST_NAME = "convnet3x3_f32_kernel";
-const char* const GENERAL_NAME = "conv_f32_kernel";
 
 inline unsigned blocks_for(long long total) { return (unsigned)((total + NT - 1) / NT); }
-
-// ------------------------------------------------------------ fast 3 x 3 conv ------------------------------------------------------------
-struct FastP {
-  const float* x; const float* w; const float* bias; float* out;
-  int H, W, Cin, Cout, relu;
-  long long M, ldx, ldo;
-};
-
-__global__ __launch_bounds__(NT) void convnet3x3_f32_kernel(FastP p) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  float* const As = smem;                      // [2][FM][FLDA]
-  float* const Bs = smem + 2 * F_A;            // [2][FK][FLDB]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const long long m0 = (long long)blockIdx.x * FM;
-  const int n0 = blockIdx.y * FN;
-
-  // A loader: this thread reads the 16-byte chunk aq of rows ar + 32 j; B loader: chunk bq of K rows br + 8 j
-  const int aq = tid & 7, ar = tid >> 3;
-  const int bq = tid & 31, br = tid >> 5;
-  long long poff[4];
-  unsigned vmask[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const long long m = m0 + ar + 32 * j;
-    poff[j] = 0;
-    vmask[j] = 0;                              // a row past M has no valid tap
-    if (m < p.M) {
-      const long long hw = (long long)p.H * p.W, img = m / hw;
-      const int r = (int)(m - img * hw), oy = r / p.W, ox = r - oy * p.W;
-      poff[j] = m * p.ldx + aq * 4;
-#pragma unroll
-      for (int t = 0; t < 9; ++t) {
-        const int iy = oy + t / 3 - 1, ix = ox + t % 3 - 1;
-        if (iy >= 0 && iy < p.H && ix >= 0 && ix < p.W) vmask[j] |= 1u << t;
-      }
-    }
-  }
-  const bool bvalid = n0 + bq * 4 < p.Cout;    // cout % 4 == 0: a chunk is inside or outside as a whole
-  const float* wp = p.w + (long long)br * p.Cout + n0 + bq * 4;
-
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-  const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64, l31 = lane & 31, half = lane >> 5;
-
-  // K walk state: tap (ky, kx) and the first channel ci of the step, advanced by additions
-  int tap = 0, kx = 0, ci = 0;
-  long long toff = -((long long)p.W + 1) * p.ldx;            // pixel offset of tap (ky - 1, kx - 1), in floats
-  const long long wstep = (long long)FK * p.Cout;
-  f32x4 av[4], bv[4];
-  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-
-  auto load = [&]() {
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      av[j] = ((vmask[j] >> tap) & 1u) ? *(const f32x4*)(p.x + poff[j] + toff + ci) : zero4;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) bv[j] = bvalid ? *(const f32x4*)(wp + (long long)(8 * j) * p.Cout) : zero4;
-    wp += wstep;
-    ci += FK;
-    if (ci == p.Cin) {
-      ci = 0;
-      ++tap;
-      toff += p.ldx;
-      if (++kx == 3) {
-        kx = 0;
-        toff += ((long long)p.W - 3) * p.ldx;
-      }
-    }
-  };
-  auto stage = [&](int buf) {
-    float* a = As + buf * F_A;
-    float* b = Bs + buf * F_B;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      float* d = a + (ar + 32 * j) * FLDA + aq * 4;
-      d[0] = av[j][0]; d[1] = av[j][1]; d[2] = av[j][2]; d[3] = av[j][3];
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) *(f32x4*)(b + (br + 8 * j) * FLDB + bq * 4) = bv[j];
-  };
-
-  const int KT = 9 * (p.Cin / FK);
-  load();
-  stage(0);
-  __syncthreads();
-  for (int kt = 0; kt < KT; ++kt) {
-    const int buf = kt & 1;
-    if (kt + 1 < KT) load();                   // in flight under this step's MFMAs
-    const float* a0 = As + buf * F_A + (wm + l31) * FLDA + half;
-    const float* a1 = a0 + 32 * FLDA;
-    const float* b0 = Bs + buf * F_B + half * FLDB + wn + l31;
-#pragma unroll
-    for (int s = 0; s < FK / 2; ++s) {
-      const float x0 = a0[2 * s], x1 = a1[2 * s], y0 = b0[2 * s * FLDB], y1 = b0[2 * s * FLDB + 32];
-      acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(x0, y0, acc[0][0], 0, 0, 0);
-      acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(x0, y1, acc[0][1], 0, 0, 0);
-      acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(x1, y0, acc[1][0], 0, 0, 0);
-      acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(x1, y1, acc[1][1], 0, 0, 0);
-    }
-    if (kt + 1 < KT) stage(buf ^ 1);           // the other buffer: its readers finished before the barrier that ended step kt - 1
-    __syncthreads();
-  }
-
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int n = n0 + wn + 32 * j + l31;
-    if (n >= p.Cout) continue;
-    const float b = p.bias ? p.bias[n] : 0.f;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const long long m = m0 + wm + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * half;
-        if (m >= p.M) continue;
-        float v = acc[i][j][r] + b;
-        if (p.relu) v = fmaxf(v, 0.f);
-        p.out[m * p.ldo + n] = v;
-      }
-  }
-}
 
 // ------------------------------------------------------------------ prep ------------------------------------------------------------------
 struct Prep {
@@ -369,77 +221,12 @@ __global__ __launch_bounds__(NT) void dists_finalize_kernel(const double* __rest
   if (tid == 0) out[n] += red[0];
 }
 
-// the argument rules of dove_convnet_conv_f32, shared with the name function (which refuses silently)
-bool conv_args_ok(const dove_convnet_conv_f32_args* a, bool report) {
-#define REFUSE(cond, ...)                        \
-  do {                                           \
-    if (!(cond)) {                               \
-      if (report) dove_set_error(__VA_ARGS__);   \
-      return false;                              \
-    }                                            \
-  } while (0)
-  REFUSE(a && a->struct_size == sizeof(dove_convnet_conv_f32_args), "dove_convnet_conv_f32: struct_size %u is not the library's %zu",
-         a ? a->struct_size : 0u, sizeof(dove_convnet_conv_f32_args));
-  REFUSE(a->x && a->w && a->out, "dove_convnet_conv_f32: null x / w / out");
-  REFUSE(a->n > 0 && a->h > 0 && a->w_in > 0 && a->cin > 0 && a->cout > 0, "dove_convnet_conv_f32: n, h, w, cin, cout must be positive");
-  REFUSE(a->kh >= 1 && a->kh <= 11 && a->kw >= 1 && a->kw <= 11, "dove_convnet_conv_f32: kernel %d x %d (sides are 1 to 11)", a->kh, a->kw);
-  REFUSE(a->stride >= 1 && a->stride <= 4, "dove_convnet_conv_f32: stride %d (1 to 4)", a->stride);
-  REFUSE(a->pad_h >= 0 && a->pad_h < a->kh && a->pad_w >= 0 && a->pad_w < a->kw, "dove_convnet_conv_f32: pad %d x %d must be below the kernel %d x %d",
-         a->pad_h, a->pad_w, a->kh, a->kw);
-  REFUSE(a->h + 2 * a->pad_h >= a->kh && a->w_in + 2 * a->pad_w >= a->kw, "dove_convnet_conv_f32: image %d x %d is smaller than the kernel %d x %d",
-         a->h, a->w_in, a->kh, a->kw);
-  REFUSE(a->ldx >= a->cin && a->ldo >= a->cout, "dove_convnet_conv_f32: ldx %lld < cin %d or ldo %lld < cout %d", a->ldx, a->cin, a->ldo,
-         a->cout);
-  REFUSE((long long)a->n * a->h * a->w_in <= 0x7fffffffLL * 32 && (long long)a->n * a->h * a->w_in * a->ldx < (1LL << 46) &&
-             (long long)a->kh * a->kw * a->cin < (1 << 24),
-         "dove_convnet_conv_f32: problem too large");
-#undef REFUSE
-  return true;
-}
-
-bool conv_is_fast(const dove_convnet_conv_f32_args* a) {
-  // cout >= 128: below that the 128-wide N tile is partly empty and conv_f32_kernel's 64 x 64 tile is faster (measured on VGG16's
-  // 64 -> 64 at 2 x 720 x 1280: 2.51 ms against 1.99 ms; docs/kernels.md).  The two kernels give the same bits.
-  return a->kh == 3 && a->kw == 3 && a->stride == 1 && a->pad_h == 1 && a->pad_w == 1 && a->cin % FK == 0 && a->cout >= FN &&
-         a->cout % 4 == 0 && a->ldx % 4 == 0 && ((uintptr_t)a->x & 15) == 0 && ((uintptr_t)a->w & 15) == 0;
-}
-
 size_t lpips_ws(int n, int h, int w) { return (size_t)n * (((size_t)h * w + LP_PIX - 1) / LP_PIX) * sizeof(double); }
 size_t dists_ws(int n, int h, int w, int c) { return (size_t)n * c * (((size_t)h * w + DS_SLICE - 1) / DS_SLICE) * 5 * sizeof(double); }
 
 }  // namespace
 
 // ------------------------------------------------------------- C entries -------------------------------------------------------------
-extern "C" const char* dove_convnet_conv_f32_kernel_name(const dove_convnet_conv_f32_args* a) {
-  if (!conv_args_ok(a, false)) return "";
-  return conv_is_fast(a) ? FAST_NAME : GENERAL_NAME;
-}
-
-// The fast walk on its own (clipiqa.hip checks the arguments of dove_resnet_conv_f32 by the rule of conv_is_fast before it calls this).
-__attribute__((visibility("hidden"))) int dove_convnet3x3_fast_launch(const float* x, const float* w, const float* bias, float* out, int n, int h,
-                                                                      int w_in, int cin, int cout, int relu, long long ldx, long long ldo,
-                                                                      void* stream) {
-  FastP p;
-  p.x = x; p.w = w; p.bias = bias; p.out = out;
-  p.H = h; p.W = w_in; p.Cin = cin; p.Cout = cout; p.relu = relu;
-  p.M = (long long)n * h * w_in; p.ldx = ldx; p.ldo = ldo;
-  static PerDeviceOnce attr_set;
-  if (auto once_ = attr_set.guard())
-    (void)hipFuncSetAttribute((const void*)convnet3x3_f32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, F_LDS);
-  dim3 grid((unsigned)((p.M + FM - 1) / FM), (unsigned)((cout + FN - 1) / FN), 1);
-  hipLaunchKernelGGL(convnet3x3_f32_kernel, grid, dim3(NT), F_LDS, (hipStream_t)stream, p);
-  DOVE_CHECK_LAUNCH("dove_convnet_conv_f32");
-  return DOVE_OK;
-}
-
-extern "C" int dove_convnet_conv_f32(const dove_convnet_conv_f32_args* a, void* stream) {
-  if (!conv_args_ok(a, true)) return DOVE_EINVAL;
-  if (!conv_is_fast(a))
-    return dove_conv_f32_general_launch(a->x, a->w, a->bias, a->out, a->n, a->h, a->w_in, a->cin, a->cout, a->kh, a->kw, a->stride, a->pad_h,
-                                        a->pad_w, a->relu, a->ldx, a->ldo, stream);
-  return dove_convnet3x3_fast_launch(a->x, a->w, a->bias, a->out, a->n, a->h, a->w_in, a->cin, a->cout, a->relu, a->ldx, a->ldo, stream);
-}
-
 extern "C" int dove_percep_prep_f32(const dove_image_view* in, int n, int c, int h, int w, float pre_mul, float pre_add, const float* mean,
                                     const float* std, float* out, void* stream) {
   DOVE_CHECK_ARG(in && in->data && mean && std && out, "dove_percep_prep_f32: null view / data / mean / std / out");

@@ -232,7 +232,7 @@ SIGNATURES = {
     "dove_video_end_of_input": [_VP],
     "dove_video_need": [_VP, _PLL, _PI],
     "dove_video_step": [_VP, _VP, C.c_size_t, _PI, _PI, _VP],
-    # optical flow (csrc/flow.hip): fp32 channels-last operators with pixel strides, and the warping error
+    # optical flow (csrc/flow.hip, csrc/conv_f32.hip): fp32 channels-last operators with pixel strides, and the warping error
     "dove_conv2d_f32": [C.POINTER(Conv2dF32Args), _VP],
     "dove_instance_norm_f32": [_VP, _I, _I, _I, _I, _VP, _I, _F, _VP, C.c_size_t, _VP, _VP],
     "dove_corr_volume_f32": [_VP, _VP, _I, _I, _I, _I, _F, _VP, _VP],
@@ -243,7 +243,7 @@ SIGNATURES = {
     "dove_add_f32": [_VP, _LL, _VP, _LL, _VP, _LL, _I, _LL, _I, _VP],
     "dove_convex_upsample_f32": [_VP, _LL, _VP, _I, _I, _I, _VP, _VP],
     "dove_flow_warp_error": [_VP, _VP, _I, _VP, _VP, _I, _I, _I, _VP, C.c_size_t, _VP, _VP, _VP, _VP],
-    # perceptual metrics (csrc/percep.hip): the fp32 trunk operators and the fp64 heads of LPIPS and DISTS; mean / std are host arrays
+    # perceptual metrics (csrc/percep.hip, csrc/conv_f32.hip): the fp32 trunk operators and the fp64 heads of LPIPS and DISTS; mean / std are host arrays
     "dove_convnet_conv_f32": [C.POINTER(ConvnetConvF32Args), _VP],
     "dove_percep_prep_f32": [C.POINTER(ImageView), _I, _I, _I, _I, _F, _F, C.POINTER(C.c_float), C.POINTER(C.c_float), _VP, _VP],
     "dove_maxpool_f32": [_VP, _LL, _I, _I, _I, _I, _I, _I, _VP, _LL, _VP],
@@ -254,7 +254,7 @@ SIGNATURES = {
     "dove_niqe_features": [C.POINTER(ImageView), _I, _I, _I, _I, _VP, C.c_size_t, _VP, _VP, _VP],
     "dove_niqe_stats": [_VP, _I, _I, _VP, _VP, _VP, _VP],
     "dove_niqe_distance": [_VP, _VP, _VP, _VP, _VP],
-    # CLIP-IQA (csrc/clipiqa.hip): the fp32 ResNet operators, the attention pool and the score in fp64
+    # CLIP-IQA (csrc/clipiqa.hip, csrc/conv_f32.hip): the fp32 ResNet operators, the attention pool and the score in fp64
     "dove_resnet_conv_f32": [C.POINTER(ResnetConvF32Args), _VP],
     "dove_avgpool_cl_f32": [_VP, _LL, _I, _I, _I, _I, _VP, _LL, _VP],
     "dove_clip_attnpool_f32": [_VP, _LL, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP, _VP],

@@ -1,5 +1,5 @@
 """The no-reference metric MUSIQ (pyiqa's ``musiq``: multi-scale patches, a ResNet stem per patch, a 14-layer transformer) on the GPU in
-exact fp32 (csrc/musiq.hip and the fp32 convs / GEMMs of csrc/clipiqa.hip).
+exact fp32 (csrc/musiq.hip and the fp32 convs / GEMMs of csrc/conv_f32.hip).
 
 The definition, restated from memory of pyiqa's ``musiq_arch.py`` and ``multiscale_trans_util.py`` (INTEGRATION.md 1k lists what is
 unchecked; every such choice is a module-level constant or one small function here):

@@ -1000,7 +1000,7 @@ def attention_bias(qkv: torch.Tensor, bias: torch.Tensor, heads: int) -> torch.T
     return out
 
 
-# ---- optical flow (csrc/flow.hip): fp32 channels-last operators that read and fill channel slices ---------------------------------
+# ---- optical flow (csrc/flow.hip, its convs in csrc/conv_f32.hip): fp32 channels-last operators that read and fill channel slices -------
 def _cl_f32(t: torch.Tensor, what: str) -> int:
     """Check a float32 [N,H,W,C] tensor or channel-slice view of one (``buf[..., a:b]``) -> its pixel stride in elements."""
     if t.dtype != torch.float32 or t.dim() != 4 or not t.is_cuda:
@@ -1014,33 +1014,54 @@ def _cl_f32(t: torch.Tensor, what: str) -> int:
     return int(ld)
 
 
+def _conv_f32(fn: str, x: torch.Tensor, w: torch.Tensor, bias, out, out_size, make_args, *, w_sides=None, per_channel=(), residual=None,
+              want_name: bool = False):
+    """The middle that conv2d_f32, convnet_conv_f32 and resnet_conv_f32 share: check ``w`` (square with a side in ``w_sides`` if given),
+    ``bias`` and the ``per_channel`` (name, vector) pairs, size or check ``out`` by ``out_size(H, W, kh, kw)`` -> (ho, wo) (which raises for an
+    image that is too small), let ``make_args(ldx, ldo)`` build the entry's struct, set its pointers, and call ``dove_<fn>``."""
+    ldx = _cl_f32(x, f"{fn} x")
+    L.require_cuda(w, bias, *(v for _, v in per_channel))
+    N, H, W, cin = x.shape
+    square = w_sides is not None
+    if w.dtype != torch.float32 or w.dim() != 4 or w.shape[2] != cin or (square and (w.shape[0] != w.shape[1] or w.shape[0] not in w_sides)):
+        rule = f"[k,k,{cin},Cout] with k {' or '.join(map(str, w_sides))}" if square else f"[kh,kw,{cin},Cout]"
+        raise ValueError(f"{fn}: w {tuple(w.shape)} {w.dtype} must be float32 {rule}")
+    kh, kw, _, cout = w.shape
+    for nm, v in (("bias", bias), *per_channel):
+        if v is not None and (v.dtype != torch.float32 or v.numel() != cout):
+            raise ValueError(f"{fn}: {nm} must be float32 [{cout}]")
+    shape = (N, *out_size(H, W, kh, kw), cout)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != shape:
+        raise ValueError(f"{fn}: out {tuple(out.shape)} must be {shape}")
+    a = make_args(ldx, _cl_f32(out, f"{fn} out"))
+    a.x, a.w, a.out = x.data_ptr(), w.data_ptr(), out.data_ptr()
+    a.bias = bias.data_ptr() if bias is not None else None
+    for nm, v in per_channel:
+        setattr(a, nm, v.data_ptr() if v is not None else None)
+    if residual is not None:
+        if tuple(residual.shape) != shape:
+            raise ValueError(f"{fn}: residual {tuple(residual.shape)} must be {shape}")
+        a.ldr, a.residual = _cl_f32(residual, f"{fn} residual"), residual.data_ptr()
+    lib = L.load()
+    L.check(getattr(lib, f"dove_{fn}")(C.byref(a), L.stream_ptr()), f"dove_{fn}")
+    return (out, getattr(lib, f"dove_{fn}_kernel_name")(C.byref(a)).decode()) if want_name else out
+
+
 def conv2d_f32(x: torch.Tensor, w: torch.Tensor, bias=None, *, stride: int = 1, act: int = 0, scale=None, shift=None, out_mul: float = 1.0,
                out: torch.Tensor | None = None) -> torch.Tensor:
     """x [N,H,W,Cin] (a channel slice is fine), w float32 [kh,kw,Cin,Cout] -> out [N,Ho,Wo,Cout] = out_mul * act(scale * (conv + bias) +
     shift), zero padding k // 2.  ``out`` may be a channel slice of a wider buffer: only that slice is written."""
-    ldx = _cl_f32(x, "conv2d_f32 x")
-    L.require_cuda(w, bias, scale, shift)
-    N, H, W, cin = x.shape
-    if w.dtype != torch.float32 or w.dim() != 4 or w.shape[2] != cin:
-        raise ValueError(f"conv2d_f32: w {tuple(w.shape)} {w.dtype} must be float32 [kh,kw,{cin},Cout]")
-    kh, kw, _, cout = w.shape
-    for nm, v in (("bias", bias), ("scale", scale), ("shift", shift)):
-        if v is not None and (v.dtype != torch.float32 or v.numel() != cout):
-            raise ValueError(f"conv2d_f32: {nm} must be float32 [{cout}]")
-    ho, wo = (H + 2 * (kh // 2) - kh) // stride + 1, (W + 2 * (kw // 2) - kw) // stride + 1
-    if out is None:
-        out = torch.empty(N, ho, wo, cout, dtype=torch.float32, device=x.device)
-    elif tuple(out.shape) != (N, ho, wo, cout):
-        raise ValueError(f"conv2d_f32: out {tuple(out.shape)} must be {(N, ho, wo, cout)}")
-    a = L.Conv2dF32Args()
-    a.x, a.w, a.out = x.data_ptr(), w.data_ptr(), out.data_ptr()
-    a.bias = bias.data_ptr() if bias is not None else None
-    a.scale = scale.data_ptr() if scale is not None else None
-    a.shift = shift.data_ptr() if shift is not None else None
-    a.n, a.h, a.w_in, a.cin, a.cout, a.kh, a.kw, a.stride, a.act, a.out_mul = N, H, W, cin, cout, kh, kw, stride, act, out_mul
-    a.ldx, a.ldo = ldx, _cl_f32(out, "conv2d_f32 out")
-    L.check(L.load().dove_conv2d_f32(C.byref(a), L.stream_ptr()), "dove_conv2d_f32")
-    return out
+    def args(ldx, ldo):
+        a = L.Conv2dF32Args()
+        (a.n, a.h, a.w_in, a.cin), (a.kh, a.kw, _, a.cout) = x.shape, w.shape
+        a.stride, a.act, a.out_mul, a.ldx, a.ldo = stride, act, out_mul, ldx, ldo
+        return a
+
+    return _conv_f32("conv2d_f32", x, w, bias, out,
+                     lambda H, W, kh, kw: ((H + 2 * (kh // 2) - kh) // stride + 1, (W + 2 * (kw // 2) - kw) // stride + 1), args,
+                     per_channel=(("scale", scale), ("shift", shift)))
 
 
 def instance_norm_f32(x: torch.Tensor, relu: bool = False, resid: torch.Tensor | None = None, eps: float = 1e-5) -> torch.Tensor:
@@ -1165,7 +1186,7 @@ def flow_warp_error(img1: torch.Tensor, img2: torch.Tensor, flow_fw: torch.Tenso
     return sums, warped, mask
 
 
-# ---- perceptual metrics (csrc/percep.hip): the fp32 trunk operators and the fp64 heads of LPIPS and DISTS ---------------------------
+# ---- perceptual metrics (csrc/percep.hip, the trunk conv in csrc/conv_f32.hip): the fp32 trunk operators and the fp64 heads --------------
 def _convnet_args(x_shape, ldx: int, w_shape, stride: int, pad, relu: bool, ldo: int | None = None) -> "L.ConvnetConvF32Args":
     N, H, W, cin = x_shape
     kh, kw, _, cout = w_shape
@@ -1187,27 +1208,14 @@ def convnet_conv_f32(x: torch.Tensor, w: torch.Tensor, bias=None, *, stride: int
     """x [N,H,W,Cin] (a channel slice is fine), w float32 [kh,kw,Cin,Cout] -> out [N,Ho,Wo,Cout] = conv + bias, ReLU'd if ``relu``;
     kernels up to 11 x 11, stride 1..4, zero padding ``pad`` below the kernel.  ``out`` may be a channel slice of a wider buffer.
     ``want_name``: also return the kernel that ran."""
-    ldx = _cl_f32(x, "convnet_conv_f32 x")
-    L.require_cuda(w, bias)
-    N, H, W, cin = x.shape
-    if w.dtype != torch.float32 or w.dim() != 4 or w.shape[2] != cin:
-        raise ValueError(f"convnet_conv_f32: w {tuple(w.shape)} {w.dtype} must be float32 [kh,kw,{cin},Cout]")
-    kh, kw, _, cout = w.shape
-    if bias is not None and (bias.dtype != torch.float32 or bias.numel() != cout):
-        raise ValueError(f"convnet_conv_f32: bias must be float32 [{cout}]")
-    ho, wo = (H + 2 * pad[0] - kh) // stride + 1, (W + 2 * pad[1] - kw) // stride + 1
-    if ho < 1 or wo < 1:
-        raise ValueError(f"convnet_conv_f32: image {H} x {W} is smaller than the kernel {kh} x {kw} with padding {tuple(pad)}")
-    if out is None:
-        out = torch.empty(N, ho, wo, cout, dtype=torch.float32, device=x.device)
-    elif tuple(out.shape) != (N, ho, wo, cout):
-        raise ValueError(f"convnet_conv_f32: out {tuple(out.shape)} must be {(N, ho, wo, cout)}")
-    a = _convnet_args(x.shape, ldx, w.shape, stride, pad, relu, _cl_f32(out, "convnet_conv_f32 out"))
-    a.x, a.w, a.out = x.data_ptr(), w.data_ptr(), out.data_ptr()
-    a.bias = bias.data_ptr() if bias is not None else None
-    lib = L.load()
-    L.check(lib.dove_convnet_conv_f32(C.byref(a), L.stream_ptr()), "dove_convnet_conv_f32")
-    return (out, lib.dove_convnet_conv_f32_kernel_name(C.byref(a)).decode()) if want_name else out
+    def out_size(H, W, kh, kw):
+        ho, wo = (H + 2 * pad[0] - kh) // stride + 1, (W + 2 * pad[1] - kw) // stride + 1
+        if ho < 1 or wo < 1:
+            raise ValueError(f"convnet_conv_f32: image {H} x {W} is smaller than the kernel {kh} x {kw} with padding {tuple(pad)}")
+        return ho, wo
+
+    return _conv_f32("convnet_conv_f32", x, w, bias, out, out_size,
+                     lambda ldx, ldo: _convnet_args(x.shape, ldx, w.shape, stride, pad, relu, ldo), want_name=want_name)
 
 
 def percep_prep_f32(img: torch.Tensor, pre_mul: float, pre_add: float, mean, std, out: torch.Tensor | None = None) -> torch.Tensor:
@@ -1285,7 +1293,7 @@ def dists_layer(x: torch.Tensor, y: torch.Tensor, alpha: torch.Tensor, beta: tor
     return out
 
 
-# ---- CLIP-IQA (csrc/clipiqa.hip): the fp32 operators of CLIP RN50's ResNet, its attention pool and the prompt-pair score ------------------
+# ---- CLIP-IQA (csrc/clipiqa.hip, the tower's conv in csrc/conv_f32.hip): CLIP RN50's fp32 ResNet operators, attention pool and score ---
 def _resnet_args(x_shape, ldx: int, w_shape, stride: int, pool: int, relu: bool, ldo: int | None = None) -> "L.ResnetConvF32Args":
     N, H, W, cin = x_shape
     k, _, _, cout = w_shape
@@ -1308,33 +1316,18 @@ def resnet_conv_f32(x: torch.Tensor, w: torch.Tensor, bias=None, *, stride: int 
     relu?((conv + bias) + residual).  ``pool`` 2: the conv reads the 2 x 2 average of x (floor sizes); it and ``residual`` belong to the
     1 x 1 convs that run on pointwise_f32_kernel.  ``residual`` and ``out`` may be channel slices, and may be one tensor.
     ``want_name``: also return the kernel that ran."""
-    ldx = _cl_f32(x, "resnet_conv_f32 x")
-    L.require_cuda(w, bias)
-    N, H, W, cin = x.shape
-    if w.dtype != torch.float32 or w.dim() != 4 or w.shape[2] != cin or w.shape[0] != w.shape[1] or w.shape[0] not in (1, 3):
-        raise ValueError(f"resnet_conv_f32: w {tuple(w.shape)} {w.dtype} must be float32 [k,k,{cin},Cout] with k 1 or 3")
-    k, _, _, cout = w.shape
-    if bias is not None and (bias.dtype != torch.float32 or bias.numel() != cout):
-        raise ValueError(f"resnet_conv_f32: bias must be float32 [{cout}]")
     if pool not in (1, 2) or stride not in (1, 2):
         raise ValueError(f"resnet_conv_f32: pool {pool} and stride {stride} must be 1 or 2")
-    ho, wo = (H // pool + 2 * (k // 2) - k) // stride + 1, (W // pool + 2 * (k // 2) - k) // stride + 1
-    if ho < 1 or wo < 1:
-        raise ValueError(f"resnet_conv_f32: image {H} x {W} is too small for pool {pool}")
-    if out is None:
-        out = torch.empty(N, ho, wo, cout, dtype=torch.float32, device=x.device)
-    elif tuple(out.shape) != (N, ho, wo, cout):
-        raise ValueError(f"resnet_conv_f32: out {tuple(out.shape)} must be {(N, ho, wo, cout)}")
-    a = _resnet_args(x.shape, ldx, w.shape, stride, pool, relu, _cl_f32(out, "resnet_conv_f32 out"))
-    a.x, a.w, a.out = x.data_ptr(), w.data_ptr(), out.data_ptr()
-    a.bias = bias.data_ptr() if bias is not None else None
-    if residual is not None:
-        if tuple(residual.shape) != (N, ho, wo, cout):
-            raise ValueError(f"resnet_conv_f32: residual {tuple(residual.shape)} must be {(N, ho, wo, cout)}")
-        a.ldr, a.residual = _cl_f32(residual, "resnet_conv_f32 residual"), residual.data_ptr()
-    lib = L.load()
-    L.check(lib.dove_resnet_conv_f32(C.byref(a), L.stream_ptr()), "dove_resnet_conv_f32")
-    return (out, lib.dove_resnet_conv_f32_kernel_name(C.byref(a)).decode()) if want_name else out
+
+    def out_size(H, W, k, _):
+        ho, wo = (H // pool + 2 * (k // 2) - k) // stride + 1, (W // pool + 2 * (k // 2) - k) // stride + 1
+        if ho < 1 or wo < 1:
+            raise ValueError(f"resnet_conv_f32: image {H} x {W} is too small for pool {pool}")
+        return ho, wo
+
+    return _conv_f32("resnet_conv_f32", x, w, bias, out, out_size,
+                     lambda ldx, ldo: _resnet_args(x.shape, ldx, w.shape, stride, pool, relu, ldo), w_sides=(1, 3), residual=residual,
+                     want_name=want_name)
 
 
 def avgpool_cl_f32(x: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:

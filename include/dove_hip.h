@@ -669,7 +669,7 @@ int dove_video_need(const dove_video* v, long long* frames, int* end_of_input);
 int dove_video_step(dove_video* v, void* out, size_t out_bytes, int* frames_written, int* done, void* stream);
 void dove_video_close(dove_video* v);
 
-/* Optical flow (RAFT) and the warping error (csrc/flow.hip).  Everything is fp32 on the f32-input MFMA or the fp32 / fp64
+/* Optical flow (RAFT) and the warping error (csrc/flow.hip, the convs in csrc/conv_f32.hip).  Everything is fp32 on the f32-input MFMA or the fp32 / fp64
  * VALU; activations are channels-last [n][h][w][c] fp32 whose pixel stride (ldx, ldo, ld...) may exceed c, so an operator reads or fills a
  * channel slice of a wider buffer (pass the pointer of the slice's first channel).  Nothing outside a written slice is touched.  No call
  * uses atomics: two calls give identical bits, and the result for one image does not depend on what else is in the batch.
@@ -732,7 +732,7 @@ size_t dove_flow_warp_error_workspace_bytes(int n, int h, int w);
 int dove_flow_warp_error(const void* img1, const void* img2, int dtype, const float* flow_fw, const float* flow_bw, int n, int h, int w,
                          void* ws, size_t ws_bytes, double* out, float* warped, unsigned char* mask, void* stream);
 
-/* Perceptual metrics LPIPS and DISTS (csrc/percep.hip): the operators of a VGG16 / AlexNet trunk in exact fp32 and the two
+/* Perceptual metrics LPIPS and DISTS (csrc/percep.hip, the conv in csrc/conv_f32.hip): the operators of a VGG16 / AlexNet trunk in exact fp32 and the two
  * statistical heads in fp64.  Layouts and guarantees are those of the flow block: channels-last fp32 with pixel strides, no atomics, identical
  * bits on repetition, and an image's result independent of the rest of the batch.
  *   convnet_conv_f32: out = conv + bias, then max(., 0) if relu != 0.  kh, kw in 1..11, stride 1..4, pad_h < kh, pad_w < kw (zero padding),
@@ -797,7 +797,7 @@ int dove_niqe_features(const dove_image_view* img, int n, int c, int h, int w, v
 int dove_niqe_stats(const double* features, int n, int blocks, double* mu, double* cov, int* counts, void* stream);
 int dove_niqe_distance(const double* mu_a, const double* cov_a, const double* mu_b, const double* cov_b, double* out);
 
-/* CLIP-IQA (csrc/clipiqa.hip): the operators of CLIP RN50's ModifiedResNet in exact fp32, its attention pool and the
+/* CLIP-IQA (csrc/clipiqa.hip, the conv in csrc/conv_f32.hip): the operators of CLIP RN50's ModifiedResNet in exact fp32, its attention pool and the
  * prompt-pair score in fp64.  Layouts and guarantees are those of the perceptual block: channels-last fp32 with pixel strides, weights
  * [k][k][cin][cout] (BatchNorm folded in by the host), no atomics, identical bits on repetition, an image's result independent of the batch.
  *   resnet_conv_f32: out = relu?((conv + bias) + residual).  k in {1, 3} with zero padding k / 2, stride in {1, 2}; pool in {1, 2}: with 2 the

@@ -136,6 +136,30 @@ def test_kernel_name_is_a_function_of_the_shape(lib, percep):
         assert lib.dove_convnet_conv_f32_kernel_name(C.byref(conv_args(cin, cout))) == FAST
 
 
+def test_routing_is_as_recorded(lib):
+    """tests/golden/conv_f32_routing.json (tools/make_conv_routing_golden.py) holds the kernel that dove_convnet_conv_f32 and
+    dove_resnet_conv_f32 chose, '' for a refusal, over a grid that crosses every routing rule, recorded before the fp32 convs were given
+    one dispatch.  Every row must still give that name."""
+    with open(os.path.join(ROOT, "tests", "golden", "conv_f32_routing.json")) as f:
+        rec = json.load(f)
+    assert rec["fields"] == ["entry", "k", "stride", "pad", "cin", "cout", "ldx", "x", "pool", "h", "w", "name"] and len(rec["rows"]) > 5000
+    assert set(rec["names"]) == {"", "conv_f32_kernel", "convnet3x3_f32_kernel", "convnet3x3_n64_f32_kernel", "pointwise_f32_kernel"}
+    wrong = []
+    for row in rec["rows"]:
+        entry, k, stride, pad, cin, cout, ldx, x, pool, h, w, name = row
+        a = (L.ConvnetConvF32Args, L.ResnetConvF32Args)[entry]()
+        a.x, a.w, a.out = x, 256, 256
+        a.n, a.h, a.w_in, a.cin, a.cout, a.stride, a.relu, a.ldx, a.ldo = 2, h, w, cin, cout, stride, 1, ldx, cout
+        if entry == 0:
+            a.kh, a.kw, a.pad_h, a.pad_w = k, k, pad, pad
+        else:
+            a.k, a.pool = k, pool
+        got = getattr(lib, rec["entries"][entry] + "_kernel_name")(C.byref(a)).decode()
+        if got != rec["names"][name]:
+            wrong.append((row, got))
+    assert not wrong, (len(wrong), wrong[:5])
+
+
 # ---- weights --------------------------------------------------------------------------------------------------------------------------
 def test_random_states_are_reproducible_with_healthy_magnitudes(percep):
     for net in ("alex", "vgg"):

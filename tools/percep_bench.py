@@ -1,7 +1,7 @@
-"""Time the trunk convolutions of LPIPS / DISTS (csrc/percep.hip) and the metrics themselves.  Nothing here is a gate.
+"""Time the trunk convolutions of LPIPS / DISTS (csrc/conv_f32.hip) and the metrics themselves.  Nothing here is a gate.
 
 For one frame pair (two images through the trunk as one batch) every conv layer of VGG16 and AlexNet is timed on both walks of
-``dove_convnet_conv_f32``: ``convnet3x3_f32_kernel`` where the shape takes it, and ``conv_f32_kernel`` (flow.hip's kernel, reached through
+``dove_convnet_conv_f32``: ``convnet3x3_f32_kernel`` where the shape takes it, and ``conv_f32_kernel`` (the general walk, reached through
 ``ops.conv2d_f32`` for the 3 x 3 layers, which is the same launch) - each the median of ``--reps`` launches bracketed by events, with the
 achieved TFLOP/s (2 * M * N * K) against the 155 TFLOP/s the f32-input MFMA reaches on this chip (docs/measurement.md).  Then the wall time
 of ``percep.lpips`` (alex, vgg) and ``percep.dists`` on a clip of ``--frames`` uint8 frames.  Weights are the rule-generated ones: the time
