@@ -13,7 +13,7 @@ the same again with a shuffled tail that ends at 1 / scale of the input size.  I
 The draws follow the reference's *distributions*, not its random streams: the reference mixes Python's ``random`` with numpy's global
 state, so no seed reproduces it.  Here all host draws come from ``numpy.random.Generator(PCG64(seed))`` in one fixed order:
 
-  for stage 1, then stage 2:  random_blur, random_resize, random_noise, random_jpeg, (random_mpeg: recorded as skipped);
+  for stage 1, then stage 2:  random_blur, random_resize, random_noise, random_jpeg, (random_mpeg: no draw from this generator);
   then the permutation of stage 2's degradation_with_shuffle, then its entries in the shuffled order (a group keeps its inner order).
   Every step first draws its ``prob`` uniform (also when ``prob`` is absent), then, if it runs:
     blur:   family, kernel size, sigma_x, sigma_y, angle, beta_gaussian, beta_plateau, omega; then per frame after the first the six
@@ -23,10 +23,20 @@ state, so no seed reproduces it.  Here all host draws come from ``numpy.random.G
     jpeg:   quality, then one walk increment per frame after the first (rounded and clipped as the reference does).
 The device noise of a recipe uses ``dove_randn``'s Philox streams (recipe seed, stream id = the noise step's number in the recipe).
 
-Departures, each recorded or refused: video-codec steps (``random_mpeg``, ``RandomVideoCompression``) are recorded as skipped - there is
-no codec in this build; ``resize_step != 0``, ``lanczos`` and unknown step types are refused; a blur-kernel size whose half-width is not
-smaller than the current frame (where one reflection does not suffice) is left out of the size draw, and a blur with no size left is
-recorded as skipped; a drawn target size is at least 1 (2 with ``is_size_even``).
+Video-codec steps (``random_mpeg``, ``RandomVideoCompression``) are recorded as skipped by default: nothing here encodes or decodes a real
+bitstream.  ``Degrader(..., video_codec="sim")`` runs them as ``ops.vcodec_roundtrip`` instead (csrc/vcodec.hip; tests/vcodec_ref.py is
+the definition): closed groups of ``gop`` frames, I then P frames with full-search integer motion per 16x16 macroblock, the H.264 4x4
+transform and quantiser on Y'CbCr 4:2:0, and one QP per group found against ``bitrate`` bits per frame under an integer bit-count model.
+It is what such a codec does to the pixels - blocking, ringing, errors that drift from frame to frame until the next I frame - and not a
+codec: no sub-pel motion, no B frames, no intra macroblocks in P frames, no deblocking filter, no entropy coding, and the drawn codec name
+(libx264 / h264 / mpeg4) is recorded without changing the arithmetic.  The k-th codec step of a recipe draws from a generator of its own,
+``PCG64([seed, VCODEC_STREAM, k])``: ``prob``, the codec name over ``codec_prob``, then ``bitrate = integers(lo, hi + 1)`` - so every
+other step of the recipe is the same with and without the option.  The step couples the frames of a group: ``apply_recipe`` takes a
+recipe with a ``vcodec`` step only in blocks that start and end on group boundaries (or at the recipe's last frame).
+
+Other departures, each recorded or refused: ``resize_step != 0``, ``lanczos`` and unknown step types are refused; a blur-kernel size
+whose half-width is not smaller than the current frame (where one reflection does not suffice) is left out of the size draw, and a blur
+with no size left is recorded as skipped; a drawn target size is at least 1 (2 with ``is_size_even``).
 """
 from __future__ import annotations
 
@@ -41,6 +51,9 @@ RESIZE_MODES = {"bilinear": 0, "bicubic": 1, "area": 2}          # L.RESIZE_*
 RECIPE_VERSION = 1
 _CODEC_STEPS = ("RandomVideoCompression",)
 _NO_CODEC = "no video codec in this build"
+VIDEO_CODECS = (None, "sim")
+VCODEC_STREAM = 0x76636F64                                       # "vcod": second word of the codec steps' own PCG64 seed
+DEFAULT_GOP = 8
 
 
 # ---- blur-kernel families ---------------------------------------------------------------------------------------------------------
@@ -136,11 +149,16 @@ class Degrader:
     _STAGE_STEPS = (("random_blur", "RandomBlur"), ("random_resize", "RandomResize"), ("random_noise", "RandomNoise"),
                     ("random_jpeg", "RandomJPEGCompression"), ("random_mpeg", "RandomVideoCompression"))
 
-    def __init__(self, config, scale: int = 4, seed: int = 42):
+    def __init__(self, config, scale: int = 4, seed: int = 42, video_codec: str | None = None, gop: int = DEFAULT_GOP):
         self.config = load_config(config)
         self.scale, self.seed = scale, int(seed)
         if scale <= 0:
             raise ValueError(f"scale {scale} must be positive")
+        if video_codec not in VIDEO_CODECS:
+            raise ValueError(f"video_codec {video_codec!r}: None (codec steps are recorded as skipped) or 'sim'")
+        if int(gop) != gop or gop <= 0:
+            raise ValueError(f"gop {gop!r} must be a positive integer")
+        self.video_codec, self.gop = video_codec, int(gop)
         self.stages = []
         for name in ("degradation_1", "degradation_2"):
             if name not in self.config:
@@ -168,6 +186,8 @@ class Degrader:
     @staticmethod
     def _check(typ, params):
         if typ in _CODEC_STEPS:
+            if "codec" in params and len(params["codec"]) != len(params.get("codec_prob", ())):
+                raise ValueError("RandomVideoCompression: codec and codec_prob differ in length")
             return
         if typ == "RandomResize":
             for opt, p in zip(params["resize_opt"], params["resize_prob"]):
@@ -192,7 +212,7 @@ class Degrader:
         """The recipe for a clip of ``frames`` frames of ``height`` x ``width`` (``seed`` overrides the Degrader's)."""
         seed = self.seed if seed is None else int(seed)
         rng = np.random.Generator(np.random.PCG64(seed))
-        st = {"rng": rng, "F": int(frames), "h": int(height), "w": int(width), "streams": 0, "steps": []}
+        st = {"rng": rng, "F": int(frames), "h": int(height), "w": int(width), "streams": 0, "steps": [], "seed": seed, "codecs": 0}
         target = (int(height / self.scale), int(width / self.scale))
         for name, steps, shuffle in self.stages:
             for typ, params in steps:
@@ -216,7 +236,18 @@ class Degrader:
     def _draw(self, st, stage, typ, params):
         rng, F = st["rng"], st["F"]
         if typ in _CODEC_STEPS:
-            st["steps"].append({"op": "skipped", "stage": stage, "type": typ, "reason": _NO_CODEC})
+            if self.video_codec is None:
+                st["steps"].append({"op": "skipped", "stage": stage, "type": typ, "reason": _NO_CODEC})
+                return
+            own = np.random.Generator(np.random.PCG64([st["seed"], VCODEC_STREAM, st["codecs"]]))
+            st["codecs"] += 1
+            if own.random() > params.get("prob", 1):
+                st["steps"].append({"op": "skipped", "stage": stage, "type": typ, "reason": "prob"})
+                return
+            codec = params["codec"][_choice(own, params["codec_prob"])]
+            lo, hi = params["bitrate"]
+            st["steps"].append({"op": "vcodec", "stage": stage, "codec": str(codec), "bitrate": int(own.integers(int(lo), int(hi) + 1)),
+                                "gop": self.gop})
             return
         if rng.random() > params.get("prob", 1):
             st["steps"].append({"op": "skipped", "stage": stage, "type": typ, "reason": "prob"})
@@ -291,9 +322,24 @@ def _frame_slice(values, frame0: int, n: int, what: str):
     return values[frame0:frame0 + n]
 
 
+def check_block(recipe: dict, frame0: int, n: int):
+    """A ``vcodec`` step codes closed groups of ``gop`` frames: a block of n frames from frame0 must start on a group boundary and end on one
+    or at the recipe's last frame, or the result would depend on the split."""
+    for i, step in enumerate(recipe["steps"]):
+        if step["op"] != "vcodec":
+            continue
+        gop = int(step["gop"])
+        if gop <= 0:
+            raise ValueError(f"recipe step {i} (vcodec): gop {gop} must be positive")
+        if frame0 % gop != 0 or ((frame0 + n) % gop != 0 and frame0 + n != recipe["frames"]):
+            raise ValueError(f"recipe step {i} (vcodec) codes groups of {gop} frames: frames {frame0}..{frame0 + n - 1} of {recipe['frames']} "
+                             f"do not start and end on a group boundary - give --block a multiple of the group length {gop}")
+
+
 def apply_recipe(frames_u8, recipe: dict, frame0: int = 0):
     """frames_u8: uint8 [F,H,W,3] (a tensor on the HIP device, or a host tensor / array that is moved there) -> uint8 [F,h,w,3] on the
-    device: uint8(clip(x, 0, 255)) of the recipe's last step.  ``frame0``: the clip index of the first frame given."""
+    device: uint8(clip(x, 0, 255)) of the recipe's last step.  ``frame0``: the clip index of the first frame given.  A recipe with a
+    ``vcodec`` step takes whole groups only (``check_block``)."""
     import torch
 
     from . import ops
@@ -305,6 +351,7 @@ def apply_recipe(frames_u8, recipe: dict, frame0: int = 0):
     if list(t.shape[1:3]) != list(recipe["input_size"]):
         raise ValueError(f"apply_recipe: frames are {tuple(t.shape[1:3])}, the recipe was drawn for {tuple(recipe['input_size'])}")
     n = t.shape[0]
+    check_block(recipe, frame0, n)
     x = t.cuda().contiguous().float()
     last_u8 = None
     for i, step in enumerate(recipe["steps"]):
@@ -327,6 +374,9 @@ def apply_recipe(frames_u8, recipe: dict, frame0: int = 0):
             x = fn(x, level, step["gray"], recipe["seed"], step["stream_id"], frame0)
         elif op == "jpeg":
             last_u8 = ops.jpeg_roundtrip(x, _frame_slice(step["quality"], frame0, n, f"{i} (jpeg)"))
+            x = last_u8.float()
+        elif op == "vcodec":
+            last_u8 = ops.vcodec_roundtrip(x, step["bitrate"], step["gop"])
             x = last_u8.float()
         else:
             raise ValueError(f"recipe step {i}: unknown op {op!r}")
@@ -401,10 +451,14 @@ def degrade_clip(path, out_stem, args, recipe=None):
             if args.preset == "bicubic":
                 recipe = bicubic_recipe(clip.frames, clip.height, clip.width, args.scale)
             else:
-                recipe = Degrader(args.config, args.scale, args.seed).recipe(clip.frames, clip.height, clip.width)
+                codec = None if getattr(args, "video_codec", "none") == "none" else args.video_codec
+                recipe = Degrader(args.config, args.scale, args.seed, codec, getattr(args, "gop", DEFAULT_GOP)).recipe(
+                    clip.frames, clip.height, clip.width)
         elif recipe["frames"] < clip.frames or list(recipe["input_size"]) != [clip.height, clip.width]:
             raise ValueError(f"{path}: {clip.frames} frames of {clip.height} x {clip.width}, the recipe is for {recipe['frames']} of "
                              f"{recipe['input_size'][0]} x {recipe['input_size'][1]}")
+        for f0 in range(0, clip.frames, args.block):                  # before anything is read or written
+            check_block(recipe, f0, min(args.block, clip.frames - f0))
         oh, ow = recipe["output_size"]
         writer = mm = None
         if args.y4m_save:
@@ -457,6 +511,10 @@ def build_parser():
                     help="who writes the --png_save files: PIL on the host, or the GPU encoder (dove_amd.png)")
     ap.add_argument("--y4m_save", action="store_true")
     ap.add_argument("--block", type=int, default=16, help="frames read, processed and written at a time")
+    ap.add_argument("--video_codec", type=str, default="none", choices=("none", "sim"),
+                    help="'sim': run the config's video-compression steps as the GPU codec round trip (ops.vcodec_roundtrip); "
+                         "'none': record them as skipped")
+    ap.add_argument("--gop", type=int, default=DEFAULT_GOP, help="frames per closed group of --video_codec sim (--block must be a multiple)")
     ap.add_argument("--fps", type=int, default=16)
     ap.add_argument("--save_format", type=str, default="yuv444p")
     ap.add_argument("--yuv_matrix", type=str, default="bt601", choices=("bt601", "bt709"))
@@ -472,6 +530,10 @@ def main(argv=None):
         raise ValueError("give exactly one of --config, --preset and --recipe_in")
     if args.block <= 0:
         raise ValueError(f"--block {args.block} must be positive")
+    if args.gop <= 0:
+        raise ValueError(f"--gop {args.gop} must be positive")
+    if args.video_codec != "none" and args.block % args.gop != 0:
+        raise ValueError(f"--block {args.block} must be a multiple of --gop {args.gop}: a group of frames is coded as a whole")
     recipe = None
     if args.recipe_in:
         with open(args.recipe_in) as f:

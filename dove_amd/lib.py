@@ -225,6 +225,8 @@ SIGNATURES = {
     "dove_add_gaussian_noise_f32": [_VP, _I, _I, _I, C.POINTER(C.c_float), _I, _ULL, _ULL, _LL, _VP, _VP],
     "dove_add_poisson_noise_f32": [_VP, _I, _I, _I, C.POINTER(C.c_float), _I, _ULL, _ULL, _LL, _VP, C.c_size_t, _VP, _VP],
     "dove_jpeg_roundtrip": [_VP, _I, _I, _I, _PI, _VP, C.c_size_t, _VP, _VP],
+    "dove_vcodec_roundtrip": [_VP, _I, _I, _I, _LL, _I, _VP, C.c_size_t, _VP, _VP, _VP, _VP],
+    "dove_motion_search_u8": [_VP, _VP, _I, _I, _I, _I, _I, _VP, _VP, _VP],
     "dove_stitch": [_VP, _I, _I, _I, _PI, _VP, _I, _I, _I, _I, _I, _I, _VP],
     "dove_video_open": [_VP, C.POINTER(VideoParams), C.POINTER(_VP)],
     "dove_video_info": [_VP, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), _PI, _PI, _PI],
@@ -289,6 +291,7 @@ PLAIN = {"dove_last_error": (C.c_char_p, []), "dove_abi_version": (C.c_int, []),
          "dove_yuv_frame_bytes": (C.c_size_t, [_I, _I, _I]),
          "dove_poisson_noise_workspace_bytes": (C.c_size_t, [_I]),
          "dove_jpeg_roundtrip_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
+         "dove_vcodec_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I]),
          "dove_chunk_planner_need": (C.c_longlong, [_VP]),
          "dove_chunk_planner_destroy": (None, [_VP]),
          "dove_video_workspace_bytes": (C.c_size_t, [_VP, C.POINTER(VideoParams)]),

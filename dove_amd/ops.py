@@ -910,6 +910,42 @@ def jpeg_roundtrip(x: torch.Tensor, quality) -> torch.Tensor:
     return out
 
 
+def vcodec_roundtrip(x: torch.Tensor, bitrate: int, gop: int = 8, want_stats: bool = False):
+    """float32 [N,H,W,3] -> uint8 [N,H,W,3]: the video-compression step (csrc/vcodec.hip; tests/vcodec_ref.py is the definition).  Closed
+    groups of ``gop`` frames, I then P with full-search integer motion, H.264 4x4 transform and quantiser on Y'CbCr 4:2:0, one QP per group
+    found against ``bitrate`` (bits per frame) * frames.  ``want_stats``: also the QP and the bits of each group, int32 / int64 [ceil(N / gop)]."""
+    N, H, W = _frames_f32(x, "vcodec_roundtrip")
+    if int(gop) != gop or gop <= 0:
+        raise ValueError(f"vcodec_roundtrip: gop {gop!r} must be a positive integer")
+    if int(bitrate) != bitrate or bitrate < 0:
+        raise ValueError(f"vcodec_roundtrip: bitrate {bitrate!r} must be a non-negative integer (bits per frame)")
+    lib = L.load()
+    groups = -(-N // int(gop))
+    out = torch.empty(N, H, W, 3, dtype=torch.uint8, device=x.device)
+    qp = torch.empty(groups, dtype=torch.int32, device=x.device)
+    bits = torch.empty(groups, dtype=torch.int64, device=x.device)
+    ws = torch.empty(int(lib.dove_vcodec_workspace_bytes(N, H, W, int(gop))), dtype=torch.uint8, device=x.device)
+    L.check(lib.dove_vcodec_roundtrip(L.ptr(x), N, H, W, int(bitrate), int(gop), L.ptr(ws), ws.numel(), L.ptr(out), L.ptr(qp), L.ptr(bits),
+                                      L.stream_ptr()), "dove_vcodec_roundtrip")
+    return (out, qp, bits) if want_stats else out
+
+
+def motion_search_u8(cur: torch.Tensor, ref: torch.Tensor, search: int = 7, lam: int = 4):
+    """uint8 [N,H,W] planes -> (mv int32 [N, ceil(H/16), ceil(W/16), 2] as (dy, dx), sad int32 [N, .., ..]): per 16x16 macroblock of
+    ``cur`` the displacement in [-search, search]^2 into the edge-replicated ``ref`` that minimises
+    (SAD + lam (se_len(dx) + se_len(dy)), |dy| + |dx|, dy, dx), and its SAD."""
+    L.require_cuda(cur, ref)
+    if cur.dtype != torch.uint8 or ref.dtype != torch.uint8 or cur.dim() != 3 or cur.shape != ref.shape:
+        raise ValueError(f"motion_search_u8: cur {tuple(cur.shape)} {cur.dtype} and ref {tuple(ref.shape)} {ref.dtype} must be uint8 [N,H,W] "
+                         "of one shape")
+    N, H, W = cur.shape
+    mv = torch.empty(N, -(-H // 16), -(-W // 16), 2, dtype=torch.int32, device=cur.device)
+    sad = torch.empty(N, -(-H // 16), -(-W // 16), dtype=torch.int32, device=cur.device)
+    L.check(L.load().dove_motion_search_u8(L.ptr(cur), L.ptr(ref), N, H, W, int(search), int(lam), L.ptr(mv), L.ptr(sad), L.stream_ptr()),
+            "dove_motion_search_u8")
+    return mv, sad
+
+
 def stitch(chunk: torch.Tensor, piece: torch.Tensor, region: dict) -> torch.Tensor:
     """``tiling.stitch`` without the write counts (csrc/video.hip ``dove_stitch``): the valid box of ``piece`` [3,f,h,w] goes to its place in
     ``chunk`` [3,F,H,W]; both bfloat16 and contiguous, ``region`` a dict of ``tiling.get_valid_tile_region``."""

@@ -599,6 +599,27 @@ size_t dove_jpeg_roundtrip_workspace_bytes(int n, int h, int w);
 int dove_jpeg_roundtrip(const float* x, int n, int h, int w, const int* quality, void* ws, size_t ws_bytes, unsigned char* out,
                         void* stream);
 
+/* The video-compression step of the degradation pipeline (tests/vcodec_ref.py fixes every byte): what a hybrid
+ * motion-compensated transform codec does to the pixels, without a bitstream.  Not modelled: sub-pel motion, B frames, intra macroblocks in
+ * P frames, the deblocking filter, entropy coding.
+ *   vcodec_roundtrip: x [n][h][w][3] f32 on the 0..255 scale -> out [n][h][w][3] u8.  trunc(clip(x, 0, 255)), edge replication to whole
+ *     16 x 16 macroblocks, BT.601 limited-range Y'CbCr 4:2:0 (dove_rgb_to_yuv_u8; back with centre siting).  Closed groups of gop frames
+ *     (the last may be shorter): an I frame predicted as 128, then P frames predicted from the previous reconstructed frame by full-search
+ *     integer motion (range 7, cost SAD + 4 (se_len(dx) + se_len(dy))) per macroblock, chroma at half the vector.  H.264 4x4 core transform
+ *     and quantiser at one QP (0..51) per group, found per group by bisection against bitrate * frames under the integer bit-count model of
+ *     the definition.  bitrate: bits per frame.  qp_out [ceil(n / gop)] i32 and bits_out [ceil(n / gop)] i64: device memory, the chosen QP
+ *     and the bits of each group at it; either may be null.  The QP search runs on the device: no readback, no allocation; ws is device
+ *     scratch of dove_vcodec_workspace_bytes(n, h, w, gop) bytes, 256-byte aligned.
+ *   motion_search_u8: the motion search on its own.  cur, ref: [n][h][w] u8 planes, both edge-replicated (cur to whole macroblocks, ref to
+ *     wherever a vector points).  Per macroblock of frame i the (dy, dx) in [-search, search]^2 (search 0..15) that minimises
+ *     (SAD + lambda (se_len(dx) + se_len(dy)), |dy| + |dx|, dy, dx) in that order, prediction = ref[y + dy][x + dx]; se_len(v) is the
+ *     signed Exp-Golomb length.  mv_out [n][ceil(h / 16)][ceil(w / 16)][2] i32 as (dy, dx); sad_out [n][..][..] i32, the winner's SAD. */
+size_t dove_vcodec_workspace_bytes(int n, int h, int w, int gop);
+int dove_vcodec_roundtrip(const float* x, int n, int h, int w, long long bitrate, int gop, void* ws, size_t ws_bytes, unsigned char* out,
+                          int* qp_out, long long* bits_out, void* stream);
+int dove_motion_search_u8(const unsigned char* cur, const unsigned char* ref, int n, int h, int w, int search, int lambda, int* mv_out,
+                          int* sad_out, void* stream);
+
 /* The stitch of ref :712-720 for one piece: the box `valid` (piece coordinates) of piece [3][f][h][w] is copied to the box of the same size at
  * (out_t0, out_h0, out_w0) of chunk [3][f_chunk][Hs][Ws]; both bf16, contiguous.  One launch, no write counts; 16-byte loads and stores when
  * both boxes allow (the box width, every row / frame / channel stride of both arrays and both box origins multiples of 8 elements, i.e.
