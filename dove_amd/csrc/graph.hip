@@ -153,6 +153,11 @@ struct Packed { bf16_t* w = nullptr; float* bias = nullptr; bf16_t* w_first = nu
                 int cout_store() const { return (int)ru(cout, 4); } };
 struct Tensor { bf16_t* p = nullptr; int T = 0, H = 0, W = 0, C = 0; long long elems() const { return (long long)T * H * W * C; } size_t bytes() const { return (size_t)elems() * 2; } };
 struct Stats { float* stats = nullptr; };
+// conv_cache entry of one causal conv (cconv): `frames` [nb x k frames] are views into or a copy of the previous frame-batch's input.
+// owner: the arena block the entry keeps alive (that retained input, or the copy itself); stride: elements between two instances' frames
+// (dove_conv_desc.cache_stride); pair: the frames are a known bit-identical pair (what dove_conv_desc.tdup == 1 declares of the cache);
+// ev: two-stream stage only - arena event index of the batch that wrote the entry (-1: none)
+struct ConvCache { Tensor frames; void* owner = nullptr; long long stride = 0; bool pair = false; long long ev = -1; };
 
 // first-fit arena over one device allocation; offsets 256-byte aligned.
 // STREAM TRACKING (round 6; off unless a VAE stage alternates its frame-batches between two streams): allocation and release are host-side
@@ -305,21 +310,17 @@ struct dove_ctx {
   // attention operand buffers (pad rows must stay zero)
   bf16_t *Qh = nullptr, *Kh = nullptr, *Vt = nullptr; long long attn_n = 0;
   // VAE
-  std::unordered_map<std::string, Tensor> cache;        // conv_cache of the running clip (views or copies)
-  std::unordered_map<std::string, void*> cache_owner;   // arena block a cache entry keeps alive (a retained conv input) or the copy itself
-  std::unordered_map<std::string, long long> cache_stride;   // nb > 1: elements between two instances' cache frames (dove_conv_desc.cache_stride)
-  std::unordered_map<std::string, bool> cache_pair;     // the cache entry is a known bit-identical frame pair (what dove_conv_desc.tdup == 1 declares of it)
-  int nb = 1;                                           // > 1 while tiled() runs nb same-shaped tiles as one batch (Tensor.T = nb x frames)
+  std::unordered_map<std::string, ConvCache> cache;     // conv_cache of the running clip, by conv name
+  int nb = 1;                                         // > 1 while tiled() runs nb same-shaped tiles as one batch (Tensor.T = nb x frames)
   float* gn_ws = nullptr; int gn_ws_rows = 0;
   float* gn_ws2 = nullptr;                              // the second VAE stream's statistics scratch (allocated with the stream)
   // Two-stream VAE (DOVE_OPT_VAE_STREAMS, default 2; dove_amd/vae.py n_streams): the frame-batches of an un-tiled single-rank stage alternate
-  // between the caller's stream and `vae_stream2`, ordered only by one event per causal conv (`cache_ev`: recorded behind the conv and its cache
-  // copy, waited for by the next batch's conv of the same name) - one batch's HBM-bound GroupNorm kernels run beside the tail of the other's convs.
+  // between the caller's stream and `vae_stream2`, ordered only by one event per causal conv (`ConvCache::ev`: recorded where the entry is
+  // complete, waited for by the next batch's conv of the same name) - one batch's HBM-bound GroupNorm kernels run beside the tail of the other's convs.
   // Same kernels on the same inputs: bit-identical.  The arena tracks the streams (struct Arena).
   int opt_vae_streams = 2;
   hipStream_t vae_stream2 = nullptr;
   bool vae_multi = false;
-  std::unordered_map<std::string, long long> cache_ev;   // conv name -> arena event index of the batch that wrote the cache entry
   float* conv_out_bias = nullptr;                       // != NULL: decoder.conv_out runs tap-split ("decoder.conv_out.taps" + gather)
   Arena arena;
   std::string err;
@@ -501,7 +502,7 @@ int conv(dove_ctx* c, const Tensor& x, const Packed& pc, const ConvOpt& o, Tenso
   d.struct_size = (unsigned)sizeof(d);
   d.x = x.p; d.cache = o.cache ? o.cache->p : nullptr; d.w = pc.w; d.bias = pc.bias; d.resid = o.resid; d.gate = o.gate; d.out = y.p;
   d.t_in = t_in; d.h_in = x.H; d.w_in = x.W; d.cin = x.C; d.t_out = t_out; d.h_out = ho; d.w_out = wo;
-  d.nb = nb; d.cache_stride = o.cache ? o.cache_stride : 0;
+  d.nb = nb; d.cache_stride = (o.cache && nb > 1) ? o.cache_stride : 0;   // one instance has no stride
   d.w_first = (o.cache || !c->opt_weight_sums) ? nullptr : pc.w_first;
   d.w_sub = (o.up == 1 && c->opt_weight_sums) ? pc.w_sub : nullptr;
   if (o.tdup && c->opt_weight_sums && pc.w_pair && pc.kt == 3 && !(o.tdup == 2 && o.cache)) { d.tdup = o.tdup; d.w_pair = pc.w_pair; }   // dove_amd/ops.py conv
@@ -706,113 +707,72 @@ int cconv(dove_ctx* c, Tensor& x, bool x_owned, const std::string& name, ConvOpt
     if (x_owned) free_t(c, x);
     return 0;
   }
-  const int k = pc.kt - 1;
-  if (c->nb > 1) {
-    // nb same-shaped tiles in one launch (tiled()): x [nb][Ti][H][W][C]; the cache entry is nb x k frames, instance b's at p + b * stride
-    // - a view of the retained previous input when x is an arena block with >= k frames per instance, else a dense copy
-    const int nb = c->nb, Ti = x.T / nb;
-    const long long frame = (long long)x.H * x.W * x.C;
-    hipStream_t s = (hipStream_t)stream;
-    auto it = c->cache.find(name);
-    Tensor prev;
-    const bool have = it != c->cache.end();
-    if (have) { prev = it->second; o.cache = &prev; o.cache_stride = c->cache_stride[name]; }
-    const int tdup_in = o.tdup;
-    if (o.tdup == 1 && have && !c->cache_pair[name]) o.tdup = 0;   // the declaration covers the cache: only a doubled input of >= k frames leaves a pair
-    CHK(conv(c, x, pc, o, out, stream));
-    c->cache_pair[name] = tdup_in != 0 && Ti >= k;
-    void* old_owner = have ? c->cache_owner[name] : nullptr;
-    Tensor nc; nc.T = nb * k; nc.H = x.H; nc.W = x.W; nc.C = x.C;
-    if (x_owned && Ti >= k && c->arena.cap - c->arena.used > 8 * x.bytes()) {
-      nc.p = x.p + (long long)(Ti - k) * frame;
-      c->cache[name] = nc; c->cache_owner[name] = x.p; c->cache_stride[name] = (long long)Ti * frame;
-      c->arena.release(old_owner);
-      x.p = nullptr;
-      return 0;
-    }
-    nc.p = (bf16_t*)c->arena.alloc(nc.bytes(), true);
-    if (!nc.p) { dove_set_error("workspace exhausted (conv cache of %s: %zu bytes)", name.c_str(), nc.bytes()); return DOVE_EINVAL; }
-    if (Ti >= k) {
-      CHK(copy2d(nc.p, (size_t)k * frame * 2, x.p + (long long)(Ti - k) * frame, (size_t)Ti * frame * 2, (size_t)k * frame * 2, nb, s));
+  // x [nb][Ti][H][W][C]: nb same-shaped tiles in one launch (tiled()), or the one instance of an un-tiled stage.  The halo exchange and the
+  // two streams belong to the un-tiled stage alone: tiled() refuses nranks > 1, VaeStreams::begin declines nb > 1
+  const int k = pc.kt - 1, nb = c->nb, Ti = x.T / nb;
+  DOVE_CHECK_ARG(nb == 1 || !(c->halo_recv || c->halo_send || c->vae_multi), "cconv(%s): a batch of tiles inside a sharded or two-stream stage", name.c_str());
+  const long long frame = (long long)x.H * x.W * x.C;
+  hipStream_t s = (hipStream_t)stream;
+  ConvCache nc; nc.frames.T = nb * k; nc.frames.H = x.H; nc.frames.W = x.W; nc.frames.C = x.C;
+  auto it = c->cache.find(name);
+  if (c->halo_recv && it == c->cache.end()) {
+    // first batch of a rank > 0: the conv_cache the previous batch would have left arrives from rank - 1 (same layer order there)
+    ConvCache h = nc;
+    CHK(halo_fetch(c, name, h.frames.bytes(), &h.owner, stream));   // lands on the context's receive stream; this stream only waits on its event
+    h.frames.p = (bf16_t*)h.owner; h.stride = (long long)k * frame;
+    h.pair = true;                                             // the previous rank's last frames: the same declaration holds there
+    it = c->cache.emplace(name, h).first;
+  }
+  const bool have = it != c->cache.end();
+  const ConvCache prev = have ? it->second : ConvCache();
+  if (have) { o.cache = &prev.frames; o.cache_stride = prev.stride; }
+  // two streams: the entry was written on the OTHER one - behind its conv and its cache copy
+  if (c->vae_multi && prev.ev >= 0) HIPCHK(hipStreamWaitEvent(s, c->arena.pool[(size_t)prev.ev], 0));
+  auto mark = [&]() -> int {                                  // ... and this batch's entry is complete from here on
+    if (!c->vae_multi) return 0;
+    nc.ev = c->arena.next_event();
+    HIPCHK(hipEventRecord(c->arena.pool[(size_t)nc.ev], s));
+    return 0;
+  };
+  nc.pair = o.tdup != 0 && Ti >= k;                          // a doubled input of >= k frames leaves a pair
+  if (o.tdup == 1 && have && !prev.pair) o.tdup = 0;          // the declaration covers the cache: a slid window of a short batch is not a pair (three taps, not two)
+  // retained view: the next batch's halo IS the tail of this conv's input, complete before the conv runs - the other stream may start its
+  // conv of this name as soon as that input exists (dove_amd/vae.py records its event at the same point)
+  const bool retain = x_owned && Ti >= k && c->arena.cap - c->arena.used > 8 * x.bytes();
+  if (retain) CHK(mark());
+  CHK(conv(c, x, pc, o, out, stream));
+  if (retain) {
+    nc.frames.p = x.p + (long long)(Ti - k) * frame;          // a view of every instance's last k frames, x stays alive
+    nc.owner = x.p; nc.stride = (long long)Ti * frame;
+    x.p = nullptr;
+  } else {
+    nc.frames.p = (bf16_t*)c->arena.alloc(nc.frames.bytes(), true);
+    if (!nc.frames.p) { dove_set_error("workspace exhausted (conv cache of %s: %zu bytes)", name.c_str(), nc.frames.bytes()); return DOVE_EINVAL; }
+    nc.owner = nc.frames.p; nc.stride = (long long)k * frame;
+    if (Ti >= k && nb == 1) {
+      HIPCHK(hipMemcpyAsync(nc.frames.p, x.p + (long long)(Ti - k) * frame, (size_t)k * frame * 2, hipMemcpyDeviceToDevice, s));
+    } else if (Ti >= k) {
+      CHK(copy2d(nc.frames.p, (size_t)k * frame * 2, x.p + (long long)(Ti - k) * frame, (size_t)Ti * frame * 2, (size_t)k * frame * 2, nb, s));
     } else {                                                    // fewer frames than the halo: slide each instance's padded window
-      const long long pstride = have ? c->cache_stride[name] : 0;
       for (int b = 0; b < nb; ++b) {
-        bf16_t* dst = nc.p + (long long)b * k * frame;
+        bf16_t* dst = nc.frames.p + (long long)b * k * frame;
         const bf16_t* xb = x.p + (long long)b * Ti * frame;
-        for (int j = 0; j < k - Ti; ++j) {
-          const bf16_t* src = have ? prev.p + (long long)b * pstride + (long long)(j + Ti) * frame : xb;
+        for (int j = 0; j < k - Ti; ++j) {                      // old cache frames move up / frame 0 replicated
+          const bf16_t* src = have ? prev.frames.p + (long long)b * prev.stride + (long long)(j + Ti) * frame : xb;
           HIPCHK(hipMemcpyAsync(dst + (long long)j * frame, src, (size_t)frame * 2, hipMemcpyDeviceToDevice, s));
         }
         HIPCHK(hipMemcpyAsync(dst + (long long)(k - Ti) * frame, xb, (size_t)Ti * frame * 2, hipMemcpyDeviceToDevice, s));
       }
     }
-    c->cache[name] = nc; c->cache_owner[name] = nc.p; c->cache_stride[name] = (long long)k * frame;
-    c->arena.release(old_owner);
-    if (x_owned) free_t(c, x);
-    return 0;
   }
-  auto it = c->cache.find(name);
-  if (c->halo_recv && it == c->cache.end()) {
-    // first batch of a rank > 0: the conv_cache the previous batch would have left arrives from rank - 1 (same layer order there)
-    Tensor h; h.T = k; h.H = x.H; h.W = x.W; h.C = x.C;
-    void* hp = nullptr;
-    CHK(halo_fetch(c, name, h.bytes(), &hp, stream));          // lands on the context's receive stream; this stream only waits on its event
-    h.p = (bf16_t*)hp;
-    c->cache[name] = h; c->cache_owner[name] = h.p;
-    c->cache_pair[name] = true;                                // the previous rank's last frames: the same declaration holds there
-    it = c->cache.find(name);
-  }
-  Tensor prev;
-  const bool have = it != c->cache.end();
-  if (have) prev = it->second;
-  o.cache = have ? &prev : nullptr;
-  if (c->vae_multi) {                                         // the entry was written on the OTHER stream: behind its conv and its cache copy
-    auto ie = c->cache_ev.find(name);
-    if (ie != c->cache_ev.end()) HIPCHK(hipStreamWaitEvent((hipStream_t)stream, c->arena.pool[(size_t)ie->second], 0));
-  }
-  auto mark = [&]() -> int {                                  // ... and this batch's entry is complete from here on
-    if (!c->vae_multi) return 0;
-    const long long e = c->arena.next_event();
-    HIPCHK(hipEventRecord(c->arena.pool[(size_t)e], (hipStream_t)stream));
-    c->cache_ev[name] = e;
-    return 0;
-  };
-  const int tdup_in = o.tdup;
-  if (o.tdup == 1 && have && !c->cache_pair[name]) o.tdup = 0;   //  a slid window of a short batch is not a pair: three taps, not two
-  // retained view (below): the next batch's halo IS the tail of this conv's input, complete before the conv runs - the other stream may
-  // start its conv of this name as soon as that input exists (dove_amd/vae.py records its event at the same point)
-  const bool retain = x_owned && x.T >= k && c->arena.cap - c->arena.used > 8 * x.bytes();
-  if (retain) CHK(mark());
-  CHK(conv(c, x, pc, o, out, stream));
-  c->cache_pair[name] = tdup_in != 0 && x.T >= k;
-  const long long frame = (long long)x.H * x.W * x.C;
-  hipStream_t s = (hipStream_t)stream;
-  void* old_owner = have ? c->cache_owner[name] : nullptr;
-  Tensor nc; nc.T = k; nc.H = x.H; nc.W = x.W; nc.C = x.C;
-  if (retain) {
-    nc.p = x.p + (long long)(x.T - k) * frame;               // retain: a view of x's last k frames, x stays alive
-    c->cache[name] = nc; c->cache_owner[name] = x.p;
-    c->arena.release(old_owner, true);                        // the conv that read the old entry is already enqueued (on this stream; the
-    x.p = nullptr;                                            // entry's producer is the other one: Arena::release `shared`)
-    if (c->halo_send) CHK(halo_publish(c, nc.p, nc.bytes(), stream));
-    return 0;
-  }
-  nc.p = (bf16_t*)c->arena.alloc(nc.bytes(), true);
-  if (!nc.p) { dove_set_error("workspace exhausted (conv cache of %s: %zu bytes)", name.c_str(), nc.bytes()); return DOVE_EINVAL; }
-  if (x.T >= k) {
-    HIPCHK(hipMemcpyAsync(nc.p, x.p + (long long)(x.T - k) * frame, (size_t)k * frame * 2, hipMemcpyDeviceToDevice, s));
-  } else {                                                    // fewer frames than the halo: slide the padded window
-    for (int j = 0; j < k - x.T; ++j) {
-      const bf16_t* src = have ? prev.p + (long long)(j + x.T) * frame : x.p;   // old cache frames move up / frame 0 replicated
-      HIPCHK(hipMemcpyAsync(nc.p + (long long)j * frame, src, (size_t)frame * 2, hipMemcpyDeviceToDevice, s));
-    }
-    HIPCHK(hipMemcpyAsync(nc.p + (long long)(k - x.T) * frame, x.p, (size_t)x.T * frame * 2, hipMemcpyDeviceToDevice, s));
-  }
-  c->cache[name] = nc; c->cache_owner[name] = nc.p;
-  c->arena.release(old_owner, true);
-  if (x_owned) free_t(c, x);
-  if (c->halo_send) CHK(halo_publish(c, nc.p, nc.bytes(), stream));
-  CHK(mark());
+  ConvCache& entry = c->cache[name];
+  entry = nc;
+  // the conv that read the old entry is already enqueued (on this stream; with two streams the entry's producer is the other one:
+  // Arena::release `shared`, which only matters while the arena tracks streams)
+  c->arena.release(prev.owner, true);
+  if (!retain && x_owned) free_t(c, x);
+  if (c->halo_send) CHK(halo_publish(c, nc.frames.p, nc.frames.bytes(), stream));
+  if (!retain) { CHK(mark()); entry.ev = nc.ev; }
   return 0;
 }
 // frames one frame-batch of t input frames leaves behind the encoder's / decoder's temporal stages (diffusers' Downsample3D
@@ -829,6 +789,14 @@ int enc_batch_frames(const dove_ctx* c, int t) {
 int dec_batch_frames(const dove_ctx* c, int t) {
   for (int i = 0; i < n_temporal_stages(c); ++i) t = t > 1 ? (t % 2 ? 2 * t - 1 : 2 * t) : 1;
   return t;
+}
+// frames a whole stage returns for n input frames: its frame-batches' sum (encoder: 1 + (n - 1) / 4 at the default batch of 8)
+int stage_out_frames(const dove_ctx* c, bool enc, int n) {
+  std::vector<std::pair<int, int>> fb;
+  frame_batches(n, enc ? c->cfg.vae_enc_batch : c->cfg.vae_dec_batch, &fb);
+  int f = 0;
+  for (auto& se : fb) f += enc ? enc_batch_frames(c, se.second - se.first) : dec_batch_frames(c, se.second - se.first);
+  return f;
 }
 // Work list per rank of the halo-exact VAE (dove_amd/dist.py plan_pieces).  With at most as many ranks as frame-batches every rank gets a
 // contiguous group of whole batches, earlier ranks take the extras.  With more ranks, batches are split in two PIECES on consecutive ranks (a
@@ -980,7 +948,7 @@ struct StageGuard {
     if (c && c->depth++ == 0) {
       clear_caches(c); c->arena.reset(); c->halo_recv = c->halo_send = false; c->nb = 1; set_piece(c, nullptr);
       c->ev_next = 0; c->halo_posted.clear(); c->halo_record.clear(); c->halo_sent = false;
-      c->vae_multi = false; c->cache_ev.clear();
+      c->vae_multi = false;
     }
   }
   ~StageGuard() { if (c) --c->depth; }
@@ -992,8 +960,7 @@ int encoder(dove_ctx* c, const Tensor& x, Tensor* out, void* stream) {
   Tensor xin = x;
   CHK(cconv(c, xin, false, c->pc.count("encoder.conv_in.taps") ? "encoder.conv_in.taps" : "encoder.conv_in", ConvOpt(), &h, stream));
   char nm[128];
-  int n_tdown = 0;
-  for (int r = cf.vae_temporal_compression; r > 1; r >>= 1) ++n_tdown;
+  const int n_tdown = n_temporal_stages(c);
   for (int i = 0; i < cf.vae_num_blocks; ++i) {
     for (int j = 0; j < cf.vae_layers_per_block; ++j) { snprintf(nm, sizeof nm, "encoder.down_blocks.%d.resnets.%d", i, j); CHK(resnet(c, &h, &hs, nm, nullptr, stream)); }
     if (i < cf.vae_num_blocks - 1) {
@@ -1027,8 +994,7 @@ int decoder(dove_ctx* c, const Tensor& z, Tensor* out, void* stream) {
   Tensor zin = z;
   CHK(cconv(c, zin, false, "decoder.conv_in", ConvOpt(), &h, stream));
   char nm[128];
-  int n_tdown = 0;
-  for (int r = cf.vae_temporal_compression; r > 1; r >>= 1) ++n_tdown;
+  const int n_tdown = n_temporal_stages(c);
   for (int j = 0; j < 2; ++j) { snprintf(nm, sizeof nm, "decoder.mid_block.resnets.%d", j); CHK(resnet(c, &h, &hs, nm, &z, stream)); }
   int tdup = 0;                                                 // the last upsampler's time map: the next block's first conv reads frame pairs
   for (int i = 0; i < cf.vae_num_blocks; ++i) {
@@ -1062,11 +1028,8 @@ int decoder(dove_ctx* c, const Tensor& z, Tensor* out, void* stream) {
   return 0;
 }
 void clear_caches(dove_ctx* c) {
-  for (auto& kv : c->cache_owner) c->arena.release(kv.second, true);
+  for (auto& kv : c->cache) c->arena.release(kv.second.owner, true);
   c->cache.clear();
-  c->cache_owner.clear();
-  c->cache_stride.clear();
-  c->cache_pair.clear();
 }
 
 // ---- DiT (dove_amd/transformer.py) ------------------------------------------------------------------------------------------------
@@ -1398,9 +1361,8 @@ extern "C" int dove_finalize_weights(dove_ctx* c) {
       const std::string n = k.substr(0, k.size() - strlen(".conv.weight"));
       // sub-pixel sums only for the upsamplers; pair sums for the first causal conv behind a TIME-doubling upsampler (decoder up-block
       // i > 0 whose predecessor compresses time: dove_amd/vae.py _pack)
-      int ub = -1, n_td = 0;
-      for (int r = cf.vae_temporal_compression; r > 1; r >>= 1) ++n_td;
-      const bool pair = sscanf(n.c_str(), "decoder.up_blocks.%d.resnets.0.conv1", &ub) == 1 && ends_with(n, ".resnets.0.conv1") && ub > 0 && ub <= n_td;
+      int ub = -1;
+      const bool pair = sscanf(n.c_str(), "decoder.up_blocks.%d.resnets.0.conv1", &ub) == 1 && ends_with(n, ".resnets.0.conv1") && ub > 0 && ub <= n_temporal_stages(c);
       Packed p; CHK(pack(c, {k}, {n + ".conv.bias"}, &p, n.find(".upsamplers.") != std::string::npos, pair)); c->pc[n] = p;
     } else if (ends_with(k, ".conv_shortcut.weight")) {
       const std::string n = k.substr(0, k.size() - strlen(".weight"));
@@ -1588,8 +1550,7 @@ static int tiled(dove_ctx* c, const Tensor& x, bool enc, int im2col_cin, Tensor*
   std::stable_sort(classes.begin(), classes.end(), [](const Cls& p, const Cls& q) {
     return (long long)p.th * p.tw * (long long)p.members.size() > (long long)q.th * q.tw * (long long)q.members.size(); });
   std::vector<void*> class_blocks;
-  int t_total = 0;
-  for (auto& se : fb) t_total += enc ? enc_batch_frames(c, se.second - se.first) : dec_batch_frames(c, se.second - se.first);
+  const int t_total = stage_out_frames(c, enc, x.T);
   int rc = 0;
   for (size_t k = 0; k < classes.size() && !rc; ++k) {
     const Cls& cl = classes[k];
@@ -1696,6 +1657,7 @@ int dove_ctx_reserve(dove_ctx* c, int F, int H, int W) { return ensure_ws(c, F, 
 struct VaeStreams {
   dove_ctx* c; hipStream_t caller;
   VaeStreams(dove_ctx* ctx, void* stream) : c(ctx), caller((hipStream_t)stream) {}
+  void forget_events() { for (auto& kv : c->cache) kv.second.ev = -1; }   // the arena's event indices mean nothing outside one tracked span
   int begin(size_t nitems) {
     c->vae_multi = false;
     if (c->opt_vae_streams < 2 || c->nranks > 1 || nitems < 2 || c->nb > 1) return 0;
@@ -1703,7 +1665,7 @@ struct VaeStreams {
     if (!c->gn_ws2) { void* m; CHK(dev_alloc(c, (size_t)c->gn_ws_rows * 64 * 4, &m)); c->gn_ws2 = (float*)m; }
     Arena& a = c->arena;
     a.begin_tracking(caller, c->vae_stream2);
-    c->cache_ev.clear();
+    forget_events();
     const long long e = a.next_event();                       // the second stream starts behind what the caller's stream holds so far (the converted clip)
     HIPCHK(hipEventRecord(a.pool[(size_t)e], caller));
     HIPCHK(hipStreamWaitEvent(c->vae_stream2, a.pool[(size_t)e], 0));
@@ -1721,71 +1683,77 @@ struct VaeStreams {
     c->vae_multi = false;
     const long long e = a.next_event();
     const hipError_t r1 = hipEventRecord(a.pool[(size_t)e], c->vae_stream2), r2 = hipStreamWaitEvent(caller, a.pool[(size_t)e], 0);
-    a.end_tracking(); c->cache_ev.clear();
+    a.end_tracking(); forget_events();
     if (r1 != hipSuccess || r2 != hipSuccess) { dove_set_error("two-stream VAE: joining the streams failed"); return DOVE_ELAUNCH; }
     return 0;
   }
   ~VaeStreams() { (void)end(); }                              // also on an early error return: nothing of this stage stays in flight un-joined
 };
 
+// This rank's work items of one stage (rank_plan: whole frame-batches, or the pieces of split ones), each through the encoder / decoder with
+// the conv caches carrying over: halos from rank - 1 into the first item and to rank + 1 out of the last, the items alternating between two
+// streams where VaeStreams allows.  `in` [n][H][W][C] is the stage's whole channels-last input; emit(i, out_first, o, stream) places item i's
+// output o, whose first frame is frame out_first of the stage's output (o is released here).
+template <class Emit>
+int run_pieces(dove_ctx* c, bool enc, const RankPlan& rp, const Tensor& in, Emit emit, void* stream) {
+  const std::string key = std::string(enc ? "enc:" : "dec:") + std::to_string(in.T) + "x" + std::to_string(in.H) + "x" + std::to_string(in.W) + ":" +
+                          std::to_string(c->nranks) + ":" + std::to_string(c->rank);
+  c->stat_halo_preposted = c->stat_halo_blocking = c->stat_halo_sent = 0;
+  VaeStreams vs(c, stream);
+  CHK(vs.begin(rp.mine.size()));
+  for (size_t i = 0; i < rp.mine.size(); ++i) {
+    void* const s = vs.item(i);
+    const Piece& pc = rp.mine[i];
+    const bool first_recv = c->nranks > 1 && i == 0 && c->rank > 0;
+    c->halo_recv = first_recv;
+    c->halo_send = c->nranks > 1 && i + 1 == rp.mine.size() && c->rank < rp.active - 1;
+    set_piece(c, &pc);
+    Tensor xb = in; xb.p = in.p + (long long)pc.s * in.H * in.W * in.C; xb.T = pc.e - pc.s;
+    Tensor o;
+    if (first_recv) CHK(halo_begin(c, key, s));
+    int rc = enc ? encoder(c, xb, &o, s) : decoder(c, xb, &o, s);
+    if (!rc && first_recv) rc = halo_end_first_item(c);
+    c->halo_recv = c->halo_send = false;
+    set_piece(c, nullptr);
+    CHK(rc);
+    CHK(emit(i, rp.out_first[i], o, s));
+    free_t(c, o);
+  }
+  return vs.end();
+}
+
 // moments [2L][T][h][w] (dtype) of x [3][F][H][W] (dtype), frame-batched like diffusers' _encode; conv caches are per call
 static int vae_encode_cl(dove_ctx* c, const void* x, int dtype, int F, int H, int W, Tensor* moments, void* stream) {
   const auto& cf = c->cfg;
+  const int T = stage_out_frames(c, true, F), h = H / 8, w = W / 8;
   Tensor xcl;
   CHK(alloc_t(c, F, H, W, c->pc.at("encoder.conv_in").cin_pad, &xcl));
+  // the clip channels-last; in im2col form when encoder.conv_in runs as a (3,1,1) conv over the 9 spatial taps
+  const bool taps = c->pc.count("encoder.conv_in.taps") != 0;
+  if (taps) CHK(dove_cl_im2col3x3_from_ncthw(x, dtype, cf.vae_in_channels, F, H, W, xcl.C, 1.0f, 0.0f, xcl.p, stream));
+  else CHK(dove_cl_from_ncthw(x, dtype, cf.vae_in_channels, (long long)F * H * W, xcl.C, 1.0f, 0.0f, xcl.p, stream));
   if (wants_tiling(c, true, H, W)) {
     DOVE_CHECK_ARG(c->nranks == 1, "vae tiling is not combined with the multi-rank halo exchange");
-    const bool taps = c->pc.count("encoder.conv_in.taps") != 0;
-    if (taps) CHK(dove_cl_im2col3x3_from_ncthw(x, dtype, cf.vae_in_channels, F, H, W, xcl.C, 1.0f, 0.0f, xcl.p, stream));
-    else CHK(dove_cl_from_ncthw(x, dtype, cf.vae_in_channels, (long long)F * H * W, xcl.C, 1.0f, 0.0f, xcl.p, stream));
     int rc = tiled(c, xcl, true, taps ? cf.vae_in_channels : 0, moments, stream);
     free_t(c, xcl);
     clear_caches(c);
-    if (!rc && (moments->T != 1 + (F - 1) / cf.vae_temporal_compression || moments->H != H / 8 || moments->W != W / 8)) {
+    if (!rc && (moments->T != T || moments->H != h || moments->W != w)) {
       dove_set_error("vae tiling: stitched moments are %d x %d x %d for a %d x %d x %d clip", moments->T, moments->H, moments->W, F, H, W);
       free_t(c, *moments);
       rc = DOVE_EINVAL;
     }
     return rc;
   }
-  if (c->pc.count("encoder.conv_in.taps")) {
-    CHK(dove_cl_im2col3x3_from_ncthw(x, dtype, cf.vae_in_channels, F, H, W, xcl.C, 1.0f, 0.0f, xcl.p, stream));
-  } else {
-    CHK(dove_cl_from_ncthw(x, dtype, cf.vae_in_channels, (long long)F * H * W, xcl.C, 1.0f, 0.0f, xcl.p, stream));
-  }
-  std::vector<std::pair<int, int>> fb;
-  frame_batches(F, cf.vae_enc_batch, &fb);
   clear_caches(c);
-  const int T = 1 + (F - 1) / cf.vae_temporal_compression, h = H / 8, w = W / 8;
   const int ld = c->pc.at("encoder.conv_out").cout_store();
   CHK(alloc_t(c, T, h, w, ld, moments));
   RankPlan rp;
   rank_plan(c, true, F, &rp);
   if (rp.total_out != T) { dove_set_error("dove_vae_encode: the rank plan yields %d latent frames, expected %d", rp.total_out, T); return DOVE_EINVAL; }
-  c->stat_halo_preposted = c->stat_halo_blocking = c->stat_halo_sent = 0;
-  VaeStreams vs(c, stream);
-  CHK(vs.begin(rp.mine.size()));
-  void* const caller_stream = stream;
-  for (size_t i = 0; i < rp.mine.size(); ++i) {
-    stream = vs.item(i);
-    const Piece& pc = rp.mine[i];
-    c->halo_recv = c->nranks > 1 && i == 0 && c->rank > 0;
-    c->halo_send = c->nranks > 1 && i + 1 == rp.mine.size() && c->rank < rp.active - 1;
-    set_piece(c, &pc);
-    Tensor xb = xcl; xb.p = xcl.p + (long long)pc.s * H * W * xcl.C; xb.T = pc.e - pc.s;
-    Tensor o;
-    const bool first_recv = c->halo_recv;
-    if (first_recv) CHK(halo_begin(c, "enc:" + std::to_string(F) + "x" + std::to_string(H) + "x" + std::to_string(W) + ":" + std::to_string(c->nranks) + ":" + std::to_string(c->rank), stream));
-    int rc = encoder(c, xb, &o, stream);
-    if (!rc && first_recv) rc = halo_end_first_item(c);
-    c->halo_recv = c->halo_send = false;
-    set_piece(c, nullptr);
-    CHK(rc);
-    HIPCHK(hipMemcpyAsync(moments->p + (long long)rp.out_first[i] * h * w * ld, o.p, o.bytes(), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    free_t(c, o);
-  }
-  stream = caller_stream;
-  CHK(vs.end());
+  CHK(run_pieces(c, true, rp, xcl, [&](size_t, int f0, const Tensor& o, void* s) -> int {
+    HIPCHK(hipMemcpyAsync(moments->p + (long long)f0 * h * w * ld, o.p, o.bytes(), hipMemcpyDeviceToDevice, (hipStream_t)s));
+    return 0;
+  }, stream));
   free_t(c, xcl);
   clear_caches(c);
   CHK(halo_stage_end(c, stream));
@@ -1822,20 +1790,7 @@ extern "C" int dove_vae_encode(dove_ctx* c, const void* x, int dtype, int F, int
 // frames the decoder returns for T latent frames: per latent frame-batch (diffusers' _decode batching) every temporal x2 stage maps
 // t frames to 2t - 1 (t odd, > 1: the first frame is not doubled), 2t (t even) or 1 (t == 1); 1 + 4(T - 1) for the odd T the
 // reference always has (clips are padded to 8N + 1 frames, ref :220-232)
-extern "C" int dove_vae_decode_num_frames(dove_ctx* c, int T) {
-  if (!c || T < 1) return 0;
-  std::vector<std::pair<int, int>> fb;
-  frame_batches(T, c->cfg.vae_dec_batch, &fb);
-  int n_tdown = 0;
-  for (int r = c->cfg.vae_temporal_compression; r > 1; r >>= 1) ++n_tdown;
-  int F = 0;
-  for (auto& se : fb) {
-    int t = se.second - se.first;
-    for (int i = 0; i < n_tdown && i < c->cfg.vae_num_blocks - 1; ++i) t = t > 1 ? (t % 2 ? 2 * t - 1 : 2 * t) : 1;
-    F += t;
-  }
-  return F;
-}
+extern "C" int dove_vae_decode_num_frames(dove_ctx* c, int T) { return c && T >= 1 ? stage_out_frames(c, false, T) : 0; }
 // z [L][T][h][w] (dtype; multiplied by `prescale` on the way in) -> video [3][F][8h][8w], F = dove_vae_decode_num_frames(T);
 // range01: clamp(x*0.5+0.5, 0, 1)
 extern "C" int dove_vae_decode(dove_ctx* c, const void* z, int dtype, int T, int h, int w, float prescale, int range01, void* video_out,
@@ -1865,50 +1820,27 @@ extern "C" int dove_vae_decode(dove_ctx* c, const void* z, int dtype, int T, int
     free_t(c, full);
     return rc;
   }
-  std::vector<std::pair<int, int>> fb;
-  frame_batches(T, cf.vae_dec_batch, &fb);
   clear_caches(c);
   const size_t esz = out_dtype == DOVE_F32 ? 4 : 2;
   RankPlan rp;
   rank_plan(c, false, T, &rp);
   if (rp.total_out != F) { dove_set_error("dove_vae_decode: the rank plan yields %d frames, expected %d", rp.total_out, F); return DOVE_EINVAL; }
-  c->stat_halo_preposted = c->stat_halo_blocking = c->stat_halo_sent = 0;
-  VaeStreams vs(c, stream);
-  CHK(vs.begin(rp.mine.size()));
-  void* const caller_stream = stream;
-  for (size_t i = 0; i < rp.mine.size(); ++i) {
-    stream = vs.item(i);
-    const Piece& pc = rp.mine[i];
-    c->halo_recv = c->nranks > 1 && i == 0 && c->rank > 0;
-    c->halo_send = c->nranks > 1 && i + 1 == rp.mine.size() && c->rank < rp.active - 1;
-    set_piece(c, &pc);
-    Tensor zb = zcl; zb.p = zcl.p + (long long)pc.s * h * w * zcl.C; zb.T = pc.e - pc.s;
-    Tensor o;
-    const bool first_recv = c->halo_recv;
-    if (first_recv) CHK(halo_begin(c, "dec:" + std::to_string(T) + "x" + std::to_string(h) + "x" + std::to_string(w) + ":" + std::to_string(c->nranks) + ":" + std::to_string(c->rank), stream));
-    int rc = decoder(c, zb, &o, stream);
-    if (!rc && first_recv) rc = halo_end_first_item(c);
-    c->halo_recv = c->halo_send = false;
-    set_piece(c, nullptr);
-    CHK(rc);
-    const int f0 = rp.out_first[i];
+  CHK(run_pieces(c, false, rp, zcl, [&](size_t, int f0, const Tensor& o, void* s) -> int {
     // [C][F][H][W] output: this piece's frames are not contiguous per channel -> convert into a staging tensor, then strided copy
     void* tmp = c->arena.alloc((size_t)cf.vae_out_channels * o.T * H * W * esz);
     DOVE_CHECK_ARG(tmp, "workspace exhausted (decoder output staging)");
     if (c->conv_out_bias) {
       CHK(dove_conv_out_gather((const float*)o.p, o.C / 2, o.T, H, W, cf.vae_out_channels, c->conv_out_bias, range01 ? 0.5f : 1.0f,
-                               range01 ? 0.5f : 0.0f, range01 ? 0.0f : -INFINITY, range01 ? 1.0f : INFINITY, tmp, out_dtype, stream));
+                               range01 ? 0.5f : 0.0f, range01 ? 0.0f : -INFINITY, range01 ? 1.0f : INFINITY, tmp, out_dtype, s));
     } else {
       CHK(dove_ncthw_from_cl(o.p, o.C, cf.vae_out_channels, (long long)o.T * H * W, range01 ? 0.5f : 1.0f, range01 ? 0.5f : 0.0f,
-                             range01 ? 0.0f : -INFINITY, range01 ? 1.0f : INFINITY, tmp, out_dtype, stream));
+                             range01 ? 0.0f : -INFINITY, range01 ? 1.0f : INFINITY, tmp, out_dtype, s));
     }
     CHK(copy2d((char*)video_out + (size_t)f0 * H * W * esz, (size_t)F * H * W * esz, tmp, (size_t)o.T * H * W * esz, (size_t)o.T * H * W * esz,
-               cf.vae_out_channels, (hipStream_t)stream));
+               cf.vae_out_channels, (hipStream_t)s));
     c->arena.release(tmp);
-    free_t(c, o);
-  }
-  stream = caller_stream;
-  CHK(vs.end());
+    return 0;
+  }, stream));
   free_t(c, zcl);
   clear_caches(c);
   CHK(halo_stage_end(c, stream));

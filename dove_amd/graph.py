@@ -5,6 +5,7 @@ class makes the same arithmetic reachable with four calls and is tested bit-for-
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import torch
 
@@ -141,12 +142,25 @@ class GraphContext:
             keep.append(tp)
         return a, keep
 
+    def latent_frames(self, F: int) -> int:
+        """Latent frames vae_encode returns for F pixel frames: every frame-batch is halved (an odd one keeps its first frame) once per
+        temporal stage - 1 + (F - 1) // 4 at the default batch of 8 frames."""
+        from .vae import frame_batches
+        stages = min(int(math.log2(self.vae_cfg.get("temporal_compression_ratio", 4))), len(self.vae_cfg["block_out_channels"]) - 1)
+        total = 0
+        for s, e in frame_batches(F, self.vae_cfg.get("num_sample_frames_batch_size", 8)):
+            t = e - s
+            for _ in range(stages):
+                t = (t + 1) // 2
+            total += t
+        return total
+
     def vae_encode(self, x: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
         """x [3,F,H,W] -> moments [2L, T, H/8, W/8] bf16 (with a multi-rank communicator only this rank's frames are written)."""
         L.require_cuda(x)
         _, F, H, W = x.shape
         lat = self.vae_cfg["latent_channels"]
-        out = out if out is not None else torch.empty(2 * lat, 1 + (F - 1) // self.vae_cfg.get("temporal_compression_ratio", 4), H // 8, W // 8, dtype=torch.bfloat16, device=x.device)
+        out = out if out is not None else torch.empty(2 * lat, self.latent_frames(F), H // 8, W // 8, dtype=torch.bfloat16, device=x.device)
         L.check(L.load().dove_vae_encode(self._h, L.ptr(x), L.dt_code(x), F, H, W, L.ptr(out), L.BF16, L.stream_ptr()), "dove_vae_encode")
         return out
 

@@ -72,9 +72,10 @@ class _Out:
 
 
 class StreamCache(dict):
-    """conv_cache for the two-stream mode: besides the halo tensors it carries, per causal conv, the HIP event recorded
-    (on the producing batch's stream) at the moment that conv's INPUT was complete -- the consuming batch, running on the
-    other stream, waits on it right before its own conv.  That is the only cross-batch dependency of the VAE."""
+    """conv_cache for the two-stream mode: besides the ``(frames, pair)`` entries it carries, per causal conv, the HIP event recorded
+    (on the producing batch's stream) at the moment the entry was complete - that conv's INPUT, whose tail the entry is a view of, or the
+    slid copy a batch shorter than the halo leaves - and the consuming batch, running on the other stream, waits on it right before it
+    reads the entry.  That is the only cross-batch dependency of the VAE."""
 
     def __init__(self):
         super().__init__()
@@ -179,62 +180,49 @@ class AutoencoderKLCogVideoX:
 
     # ---- building blocks ---------------------------------------------------------------------------
     def _cconv(self, x, name, cache, **kw):
-        """CogVideoXCausalConv3d with conv_cache: the front halo is the last kt-1 input frames of the previous batch."""
+        """CogVideoXCausalConv3d with conv_cache: the front halo is the last kt-1 input frames of the previous batch.
+
+        x is [nb*T, H, W, C]: nb same-shaped tiles in one launch (_tiled), or the one instance of an un-tiled clip.  ``cache[name]`` is
+        ``(frames, pair)``: frames [nb, k, H, W, C], instance b's first output frames read frames[b]; ``pair``: they are a bit-identical
+        frame pair (what ``tdup = 1`` declares of the cache)."""
         pc = self.pc[name]
         kw["weight_sums"] = self.weight_sums
+        nb = self._nb
         if pc.kt == 1:
-            return ops.conv(x, pc, nb=self._nb, **kw)
+            return ops.conv(x, pc, nb=nb, **kw)
         k = pc.kt - 1
-        if self._nb > 1:
-            # nb same-shaped tiles in one launch (_tiled): x [nb*T, H, W, C], the cache a [nb, k, H, W, C] view of the previous
-            # frame-batch's input - instance b's first frames read cache[b]
-            nb = self._nb
-            x5 = x.view(nb, x.shape[0] // nb, *x.shape[1:])
-            prev = cache.get(name)
-            events = getattr(cache, "events", None)    # StreamCache: the class's frame-batches alternate between two HIP streams (_tiled)
-            if events is not None:
-                ev_prev = events.get(name)
-                ev = torch.cuda.Event()
-                ev.record(cache.stream)
-                events[name] = ev
-                if ev_prev is not None:
-                    cache.stream.wait_event(ev_prev)
-                    prev.record_stream(cache.stream)
-            if x5.shape[1] >= k:
-                new = x5[:, -k:]
-            else:
-                pad = prev if prev is not None else x5[:, :1].expand(-1, k, -1, -1, -1)
-                new = torch.cat([pad, x5], dim=1)[:, -k:].contiguous()
-            cache[name] = new
-            return ops.conv(x, pc, cache=prev, nb=nb, **kw)
-        fetch = getattr(cache, "fetch", None)      # dove_amd.dist.HaloCache: halo arrives from rank-1 over xGMI
-        prev = fetch(name, (k,) + tuple(x.shape[1:]), x.device) if fetch else cache.get(name)
-        events = getattr(cache, "events", None)    # StreamCache: frame-batches alternate between two HIP streams
-        if events is not None:
-            ev_prev = events.get(name)
-            ev = torch.cuda.Event()
-            ev.record(cache.stream)                # everything that produced x (this conv's input) is ordered before it
-            events[name] = ev
-            if ev_prev is not None:
-                cache.stream.wait_event(ev_prev)
-                prev.record_stream(cache.stream)   # keep the other stream's tensor alive for this stream's read
-        tdup = kw.get("tdup", 0)
-        if tdup == 1 and prev is not None and not fetch and not cache.get(name + "#pair", False):
-            # ``tdup = 1`` also declares the CACHE a bit-identical pair.  It is one exactly when the previous batch's input was doubled and at
-            # least as long as the halo (its last two frames are then a pair); a shorter batch leaves a slid window (prev[1], x0), which is
-            # not.  frame_batches cannot produce that sequence today, but the declaration is checked here, not assumed (ADVICE r05)
-            kw["tdup"] = 0
-        if x.shape[0] >= k:
-            new = x[-k:]      # a view: conv inputs are never written again, the batch tensor simply stays alive
-        else:  # fewer frames than the halo: slide the padded window
-            pad = prev if prev is not None else x[:1].expand(k, -1, -1, -1)
-            new = torch.cat([pad, x], dim=0)[-k:].clone()
+        x5 = x.view(nb, x.shape[0] // nb, *x.shape[1:])
+        fetch = getattr(cache, "fetch", None)      # dove_amd.dist.HaloCache: halo arrives from rank-1 over xGMI; it keeps plain [k, H, W, C] tensors
         if fetch:
-            cache.publish(name, new)
+            assert nb == 1, "tiles are not batched under the halo exchange"
+            prev = fetch(name, (k,) + tuple(x.shape[1:]), x.device)
+            prev, pair = (None if prev is None else prev[None]), True      # the previous rank's last frames: never demoted here
         else:
-            cache[name] = new
-            cache[name + "#pair"] = bool(tdup) and x.shape[0] >= k      # doubled input (tmode 1: pairs from frame 0; 2: from frame 1, odd length)
-        return ops.conv(x, pc, cache=prev, **kw)
+            prev, pair = cache.get(name, (None, False))
+        events = getattr(cache, "events", None)    # StreamCache: frame-batches alternate between HIP streams
+        if events is not None and name in events:
+            cache.stream.wait_event(events[name])  # the entry was written on another stream
+            prev.record_stream(cache.stream)       # ... whose tensor stays alive for this stream's read
+        tdup = kw.get("tdup", 0)
+        if tdup == 1 and prev is not None and not pair:
+            # ``tdup = 1`` also declares the CACHE a bit-identical pair.  It is one exactly when the previous batch's input was doubled and at
+            # least as long as the halo (its last two frames are then a pair); a shorter batch leaves a slid window (prev[1], x0), which is not
+            kw["tdup"] = 0
+        if x5.shape[1] >= k:
+            new = x5[:, -k:]      # a view: conv inputs are never written again, the batch tensor simply stays alive
+        else:  # fewer frames than the halo: slide each instance's padded window
+            pad = prev if prev is not None else x5[:, :1].expand(-1, k, -1, -1, -1)
+            new = torch.cat([pad, x5], dim=1)[:, -k:].contiguous()
+        if events is not None:
+            events[name] = torch.cuda.Event()
+            events[name].record(cache.stream)      # this batch's entry is complete: the conv's input, or the slid copy of it
+        if fetch:
+            cache.publish(name, new[0])
+        else:
+            cache[name] = (new, bool(tdup) and x5.shape[1] >= k)   # doubled input (tmode 1: pairs from frame 0; 2: from frame 1, odd length)
+        if prev is not None and nb == 1:
+            prev = prev[0]
+        return ops.conv(x, pc, cache=prev, nb=nb, **kw)
 
     # set by dove_amd.dist while a rank runs a PIECE of a frame-batch (the batch is split over a rank pair):
     #   _gn_hook(x) -> stats over the whole batch (pieces' sums combined);  _piece_role: "head" / "tail" for Upsample3D's

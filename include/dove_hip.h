@@ -495,7 +495,9 @@ int dove_finalize_weights(dove_ctx* ctx);
 size_t dove_workspace_bytes(dove_ctx* ctx, int F, int H, int W);
 int dove_set_workspace(dove_ctx* ctx, void* dev_ptr, size_t bytes);
 size_t dove_workspace_high_water(dove_ctx* ctx);
-/* pipe.vae.encode(x).latent_dist.parameters (ref :408): x [3][F][H][W] -> moments [2L][T][H/8][W/8] */
+/* pipe.vae.encode(x).latent_dist.parameters (ref :408): x [3][F][H][W] -> moments [2L][T][H/8][W/8]; T is the sum over the frame-batches
+ * of what each leaves behind the temporal 2:1 stages = 1 + (F-1)/4 at the default vae_enc_batch of 8 (the counts of dove_shard_frames
+ * (ctx, 0, F, ...) over the ranks add up to it) */
 int dove_vae_encode(dove_ctx* ctx, const void* x, int dtype, int F, int H, int W, void* moments_out, int out_dtype, void* stream);
 /* pipe.transformer(...)[0] for one sample (ref :483-489): hidden [T][C][h][w], text [L][text_dim] bf16 -> v [T][C][h][w] */
 int dove_dit_forward(dove_ctx* ctx, const void* hidden, int dtype, int T, int h, int w, const void* text, int L, int timestep,

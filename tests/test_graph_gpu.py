@@ -193,6 +193,45 @@ def test_option_vae_tiling_bit_exact(both):
         ctx.enable_tiling(False)
 
 
+def test_single_frame_batches_bit_exact():
+    """Frame-batches of ONE frame (num_sample_frames_batch_size = num_latent_frames_batch_size = 1): every batch after the first is
+    shorter than the causal convs' two-frame halo, so each cache entry is the previous one slid by one frame instead of the tail of the
+    conv's input.  C graph == facade bit for bit, with one stream and with two (the slid copy is then what the other stream waits
+    for), and inside spatial tiles, where a batch of tiles slides every instance's window."""
+    from dove_amd import lib as L
+    v, t, s = config.small_configs(num_layers=2)
+    v["num_sample_frames_batch_size"] = v["num_latent_frames_batch_size"] = 1
+    seed = 37
+    wv = weights.random_state_dict(weights.vae_param_shapes(v), seed)
+    wt = weights.random_state_dict(weights.dit_param_shapes(t), seed)
+    pipe = CogVideoXPipeline.from_config(v, t, s, seed=seed, device="cuda")
+    ctx = GraphContext(v, t, wv, wt, "cuda")
+    g = torch.Generator().manual_seed(12)
+    video = (torch.rand(3, 3, 32, 48, generator=g) * 2 - 1).to(BF).cuda()
+    z = torch.randn(16, 3, 4, 6, generator=g).to(BF).cuda()
+    for n in (1, 2):
+        ctx.set_option(L.OPT_VAE_STREAMS, n)
+        pipe.vae.n_streams = n
+        m_c, m_py = ctx.vae_encode(video), pipe.vae.encode(video[None]).latent_dist.parameters[0]
+        d_c, d_py = ctx.vae_decode(z), pipe.vae.decode(z[None]).sample[0]
+        torch.cuda.synchronize()
+        assert m_c.shape == (32, 3, 4, 6) and d_c.shape == (3, 3, 32, 48)      # one frame out per one-frame batch, both ways
+        assert torch.equal(m_c, m_py), f"{n} stream(s), encode differs: {float((m_c.float() - m_py.float()).abs().max())}"
+        assert torch.equal(d_c, d_py), f"{n} stream(s), decode differs: {float((d_c.float() - d_py.float()).abs().max())}"
+    pipe.vae.config["sample_height"], pipe.vae.config["sample_width"] = 96, 160   # 48 x 80 px tiles, 3 x 3 of them, ragged last ones
+    ctx.set_option(L.OPT_VAE_SAMPLE_HEIGHT, 96)
+    ctx.set_option(L.OPT_VAE_SAMPLE_WIDTH, 160)
+    pipe.vae.enable_tiling()
+    ctx.enable_tiling()
+    video = (torch.rand(3, 3, 112, 192, generator=g) * 2 - 1).to(BF).cuda()
+    z = torch.randn(16, 3, 14, 24, generator=g).to(BF).cuda()
+    m_c, m_py = ctx.vae_encode(video), pipe.vae.encode(video[None]).latent_dist.parameters[0]
+    d_c, d_py = ctx.vae_decode(z), pipe.vae.decode(z[None]).sample[0]
+    torch.cuda.synchronize()
+    assert torch.equal(m_c, m_py), f"tiled encode differs: {float((m_c.float() - m_py.float()).abs().max())}"
+    assert torch.equal(d_c, d_py), f"tiled decode differs: {float((d_c.float() - d_py.float()).abs().max())}"
+
+
 def test_option_noise_step_bit_exact(both):
     """`--noise_step` (ref :449-457) through dove_sr_clip's pre_noise argument == process_video(noise_step=200) with the same eps."""
     pipe, ctx, _ = both

@@ -166,6 +166,35 @@ def test_vae_tiling_vs_oracle(monkeypatch):
     assert rel(pipe.vae.encode(small.to(torch.bfloat16)).latent_dist.parameters, ov.encode(small)) < 0.06
 
 
+def test_vae_single_frame_batches_vs_oracle(monkeypatch):
+    """Frame-batches of ONE frame: every batch after the first is shorter than the causal convs' two-frame halo, so each cache entry is
+    the previous entry slid by one frame (`_cconv`'s short-batch branch) - per instance when tiles run as one batch."""
+    emu_ops.install(monkeypatch)
+    v, t, s = config.tiny_configs()
+    v["num_sample_frames_batch_size"] = v["num_latent_frames_batch_size"] = 1
+    pipe = CogVideoXPipeline.from_config(v, t, s, seed=7, device="cpu")
+    ov = OracleVAE(v, weights.random_state_dict(weights.vae_param_shapes(v), 7))
+    torch.manual_seed(5)
+    for T in (1, 2, 3):
+        z = torch.randn(1, 16, T, 4, 6)
+        d, d_ref = pipe.vae.decode(z.to(torch.bfloat16)).sample, ov.decode(z)
+        assert d.shape == d_ref.shape
+        assert rel(d, d_ref) < 0.06, T
+    x = torch.randn(1, 3, 3, 32, 48).clamp(-1, 1)
+    p, p_ref = pipe.vae.encode(x.to(torch.bfloat16)).latent_dist.parameters, ov.encode(x)
+    assert p.shape == p_ref.shape
+    assert rel(p, p_ref) < 0.06
+    # the same short batches inside spatial tiles: a batch of tiles slides every instance's window like the tile-by-tile loop does
+    v["sample_height"], v["sample_width"] = 32, 48
+    pipe = CogVideoXPipeline.from_config(v, t, s, seed=7, device="cpu")
+    pipe.vae.enable_tiling()
+    z = torch.randn(1, 16, 3, 6, 9).to(torch.bfloat16)
+    assert pipe.vae.tile_batching
+    d = pipe.vae.decode(z).sample
+    pipe.vae.tile_batching = False
+    assert torch.equal(d, pipe.vae.decode(z).sample)
+
+
 def test_prepost_roundtrip_cpu(monkeypatch, tmp_path):
     """preprocess_frames / postprocess_frames / frame I/O glue (emulated ops): shapes, pads, the reference's x4 crop quirk."""
     emu_ops.install(monkeypatch)
