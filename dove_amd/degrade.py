@@ -29,7 +29,10 @@ the definition): closed groups of ``gop`` frames, I then P frames with full-sear
 transform and quantiser on Y'CbCr 4:2:0, and one QP per group found against ``bitrate`` bits per frame under an integer bit-count model.
 It is what such a codec does to the pixels - blocking, ringing, errors that drift from frame to frame until the next I frame - and not a
 codec: no sub-pel motion, no B frames, no intra macroblocks in P frames, no deblocking filter, no entropy coding, and the drawn codec name
-(libx264 / h264 / mpeg4) is recorded without changing the arithmetic.  The k-th codec step of a recipe draws from a generator of its own,
+(libx264 / h264 / mpeg4) is recorded without changing the arithmetic.  ``video_codec="sim-h264"`` draws exactly what ``"sim"`` draws and
+adds ``"tools": ["intra16", "qpel", "deblock"]`` to each ``vcodec`` step: I frames predicted per macroblock from their neighbours,
+quarter-sample motion and the in-loop deblocking filter (tests/vcodec_tools_ref.py is the definition); a step without ``tools`` runs as
+``"sim"`` does.  The k-th codec step of a recipe draws from a generator of its own,
 ``PCG64([seed, VCODEC_STREAM, k])``: ``prob``, the codec name over ``codec_prob``, then ``bitrate = integers(lo, hi + 1)`` - so every
 other step of the recipe is the same with and without the option.  The step couples the frames of a group: ``apply_recipe`` takes a
 recipe with a ``vcodec`` step only in blocks that start and end on group boundaries (or at the recipe's last frame).
@@ -51,7 +54,8 @@ RESIZE_MODES = {"bilinear": 0, "bicubic": 1, "area": 2}          # L.RESIZE_*
 RECIPE_VERSION = 1
 _CODEC_STEPS = ("RandomVideoCompression",)
 _NO_CODEC = "no video codec in this build"
-VIDEO_CODECS = (None, "sim")
+VIDEO_CODECS = (None, "sim", "sim-h264")
+VCODEC_TOOLS = ("intra16", "qpel", "deblock")                       # the names a vcodec step's "tools" may hold (ops.VCODEC_TOOLS)
 VCODEC_STREAM = 0x76636F64                                       # "vcod": second word of the codec steps' own PCG64 seed
 DEFAULT_GOP = 8
 
@@ -155,7 +159,7 @@ class Degrader:
         if scale <= 0:
             raise ValueError(f"scale {scale} must be positive")
         if video_codec not in VIDEO_CODECS:
-            raise ValueError(f"video_codec {video_codec!r}: None (codec steps are recorded as skipped) or 'sim'")
+            raise ValueError(f"video_codec {video_codec!r}: None (codec steps are recorded as skipped), 'sim' or 'sim-h264'")
         if int(gop) != gop or gop <= 0:
             raise ValueError(f"gop {gop!r} must be a positive integer")
         self.video_codec, self.gop = video_codec, int(gop)
@@ -248,6 +252,8 @@ class Degrader:
             lo, hi = params["bitrate"]
             st["steps"].append({"op": "vcodec", "stage": stage, "codec": str(codec), "bitrate": int(own.integers(int(lo), int(hi) + 1)),
                                 "gop": self.gop})
+            if self.video_codec == "sim-h264":
+                st["steps"][-1]["tools"] = list(VCODEC_TOOLS)
             return
         if rng.random() > params.get("prob", 1):
             st["steps"].append({"op": "skipped", "stage": stage, "type": typ, "reason": "prob"})
@@ -324,10 +330,13 @@ def _frame_slice(values, frame0: int, n: int, what: str):
 
 def check_block(recipe: dict, frame0: int, n: int):
     """A ``vcodec`` step codes closed groups of ``gop`` frames: a block of n frames from frame0 must start on a group boundary and end on one
-    or at the recipe's last frame, or the result would depend on the split."""
+    or at the recipe's last frame, or the result would depend on the split.  Its ``tools``, if any, are names of VCODEC_TOOLS."""
     for i, step in enumerate(recipe["steps"]):
         if step["op"] != "vcodec":
             continue
+        tools = step.get("tools", [])
+        if not isinstance(tools, (list, tuple)) or any(name not in VCODEC_TOOLS for name in tools):
+            raise ValueError(f"recipe step {i} (vcodec): tools {tools!r} must be a list of names from {list(VCODEC_TOOLS)}")
         gop = int(step["gop"])
         if gop <= 0:
             raise ValueError(f"recipe step {i} (vcodec): gop {gop} must be positive")
@@ -376,7 +385,7 @@ def apply_recipe(frames_u8, recipe: dict, frame0: int = 0):
             last_u8 = ops.jpeg_roundtrip(x, _frame_slice(step["quality"], frame0, n, f"{i} (jpeg)"))
             x = last_u8.float()
         elif op == "vcodec":
-            last_u8 = ops.vcodec_roundtrip(x, step["bitrate"], step["gop"])
+            last_u8 = ops.vcodec_roundtrip(x, step["bitrate"], step["gop"], tools=step.get("tools", ()))
             x = last_u8.float()
         else:
             raise ValueError(f"recipe step {i}: unknown op {op!r}")
@@ -511,8 +520,9 @@ def build_parser():
                     help="who writes the --png_save files: PIL on the host, or the GPU encoder (dove_amd.png)")
     ap.add_argument("--y4m_save", action="store_true")
     ap.add_argument("--block", type=int, default=16, help="frames read, processed and written at a time")
-    ap.add_argument("--video_codec", type=str, default="none", choices=("none", "sim"),
+    ap.add_argument("--video_codec", type=str, default="none", choices=("none", "sim", "sim-h264"),
                     help="'sim': run the config's video-compression steps as the GPU codec round trip (ops.vcodec_roundtrip); "
+                         "'sim-h264': the same draws with the H.264 tool set (intra prediction, quarter-sample motion, deblocking); "
                          "'none': record them as skipped")
     ap.add_argument("--gop", type=int, default=DEFAULT_GOP, help="frames per closed group of --video_codec sim (--block must be a multiple)")
     ap.add_argument("--fps", type=int, default=16)

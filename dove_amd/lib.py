@@ -226,6 +226,7 @@ SIGNATURES = {
     "dove_add_poisson_noise_f32": [_VP, _I, _I, _I, C.POINTER(C.c_float), _I, _ULL, _ULL, _LL, _VP, C.c_size_t, _VP, _VP],
     "dove_jpeg_roundtrip": [_VP, _I, _I, _I, _PI, _VP, C.c_size_t, _VP, _VP],
     "dove_vcodec_roundtrip": [_VP, _I, _I, _I, _LL, _I, _VP, C.c_size_t, _VP, _VP, _VP, _VP],
+    "dove_vcodec_roundtrip_tools": [_VP, _I, _I, _I, _LL, _I, _I, _VP, C.c_size_t, _VP, _VP, _VP, _VP],
     "dove_motion_search_u8": [_VP, _VP, _I, _I, _I, _I, _I, _VP, _VP, _VP],
     "dove_stitch": [_VP, _I, _I, _I, _PI, _VP, _I, _I, _I, _I, _I, _I, _VP],
     "dove_video_open": [_VP, C.POINTER(VideoParams), C.POINTER(_VP)],
@@ -292,6 +293,7 @@ PLAIN = {"dove_last_error": (C.c_char_p, []), "dove_abi_version": (C.c_int, []),
          "dove_poisson_noise_workspace_bytes": (C.c_size_t, [_I]),
          "dove_jpeg_roundtrip_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
          "dove_vcodec_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I]),
+         "dove_vcodec_tools_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I, _I]),
          "dove_chunk_planner_need": (C.c_longlong, [_VP]),
          "dove_chunk_planner_destroy": (None, [_VP]),
          "dove_video_workspace_bytes": (C.c_size_t, [_VP, C.POINTER(VideoParams)]),

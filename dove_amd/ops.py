@@ -910,10 +910,32 @@ def jpeg_roundtrip(x: torch.Tensor, quality) -> torch.Tensor:
     return out
 
 
-def vcodec_roundtrip(x: torch.Tensor, bitrate: int, gop: int = 8, want_stats: bool = False):
+VCODEC_TOOLS = {"intra16": 1, "qpel": 2, "deblock": 4}              # DOVE_VCODEC_* of include/dove_hip.h
+
+
+def vcodec_tools_mask(tools) -> int:
+    """An int mask of VCODEC_TOOLS bits, or an iterable of its names -> the mask.  Host code: unknown bits and names raise ValueError."""
+    if isinstance(tools, int) and not isinstance(tools, bool):
+        if tools < 0 or tools & ~sum(VCODEC_TOOLS.values()):
+            raise ValueError(f"vcodec tools {tools!r}: unknown bits (known: {VCODEC_TOOLS})")
+        return tools
+    if isinstance(tools, (str, bytes)) or not hasattr(tools, "__iter__"):
+        raise ValueError(f"vcodec tools {tools!r}: an int mask or an iterable of names from {sorted(VCODEC_TOOLS)}")
+    mask = 0
+    for name in tools:
+        if name not in VCODEC_TOOLS:
+            raise ValueError(f"vcodec tool {name!r}: one of {sorted(VCODEC_TOOLS)}")
+        mask |= VCODEC_TOOLS[name]
+    return mask
+
+
+def vcodec_roundtrip(x: torch.Tensor, bitrate: int, gop: int = 8, want_stats: bool = False, tools=0):
     """float32 [N,H,W,3] -> uint8 [N,H,W,3]: the video-compression step (csrc/vcodec.hip; tests/vcodec_ref.py is the definition).  Closed
     groups of ``gop`` frames, I then P with full-search integer motion, H.264 4x4 transform and quantiser on Y'CbCr 4:2:0, one QP per group
-    found against ``bitrate`` (bits per frame) * frames.  ``want_stats``: also the QP and the bits of each group, int32 / int64 [ceil(N / gop)]."""
+    found against ``bitrate`` (bits per frame) * frames.  ``want_stats``: also the QP and the bits of each group, int32 / int64 [ceil(N / gop)].
+    ``tools``: the H.264 tool set (tests/vcodec_tools_ref.py is its definition) as a mask or as names of VCODEC_TOOLS - "intra16" (I frames
+    predicted from their neighbours), "qpel" (quarter-sample motion), "deblock" (the in-loop edge filter); 0 is the plain codec."""
+    tools = vcodec_tools_mask(tools)
     N, H, W = _frames_f32(x, "vcodec_roundtrip")
     if int(gop) != gop or gop <= 0:
         raise ValueError(f"vcodec_roundtrip: gop {gop!r} must be a positive integer")
@@ -924,6 +946,11 @@ def vcodec_roundtrip(x: torch.Tensor, bitrate: int, gop: int = 8, want_stats: bo
     out = torch.empty(N, H, W, 3, dtype=torch.uint8, device=x.device)
     qp = torch.empty(groups, dtype=torch.int32, device=x.device)
     bits = torch.empty(groups, dtype=torch.int64, device=x.device)
+    if tools:
+        ws = torch.empty(int(lib.dove_vcodec_tools_workspace_bytes(N, H, W, int(gop), tools)), dtype=torch.uint8, device=x.device)
+        L.check(lib.dove_vcodec_roundtrip_tools(L.ptr(x), N, H, W, int(bitrate), int(gop), tools, L.ptr(ws), ws.numel(), L.ptr(out), L.ptr(qp),
+                                                L.ptr(bits), L.stream_ptr()), "dove_vcodec_roundtrip_tools")
+        return (out, qp, bits) if want_stats else out
     ws = torch.empty(int(lib.dove_vcodec_workspace_bytes(N, H, W, int(gop))), dtype=torch.uint8, device=x.device)
     L.check(lib.dove_vcodec_roundtrip(L.ptr(x), N, H, W, int(bitrate), int(gop), L.ptr(ws), ws.numel(), L.ptr(out), L.ptr(qp), L.ptr(bits),
                                       L.stream_ptr()), "dove_vcodec_roundtrip")

@@ -622,6 +622,24 @@ int dove_vcodec_roundtrip(const float* x, int n, int h, int w, long long bitrate
 int dove_motion_search_u8(const unsigned char* cur, const unsigned char* ref, int n, int h, int w, int search, int lambda, int* mv_out,
                           int* sad_out, void* stream);
 
+/* The round trip with an H.264 tool set (tests/vcodec_tools_ref.py fixes every byte).  tools is a mask of the bits below;
+ * 0 gives the bytes, QPs and bits of dove_vcodec_roundtrip, unknown bits are refused.  Every other argument is dove_vcodec_roundtrip's; ws is
+ * dove_vcodec_tools_workspace_bytes(n, h, w, gop, tools) bytes (with tools 0 the size of dove_vcodec_workspace_bytes).
+ *   INTRA16: I frames are predicted per macroblock from the row above and the column to the left of the frame's unfiltered reconstruction
+ *     (luma V / H / DC, chroma DC / H / V by SAD + 4 ue_len(index)), macroblocks in raster order: one launch per anti-diagonal.
+ *   QPEL: a P macroblock's integer winner is refined in quarter samples (two steps of 9 candidates); luma by the 6-tap (1, -5, 20, 20, -5, 1)
+ *     half samples and their averages, chroma bilinear in eighths; the vector costs its quarter-unit Exp-Golomb lengths.
+ *   DEBLOCK: the H.264 edge filter at indexA = indexB = QP on every reconstructed frame before it is output and referenced: all vertical
+ *     edges of a plane, then all horizontal ones (frame-wide, not the standard's macroblock interleave).
+ * Still not modelled: B frames, intra macroblocks in P frames, Intra 4x4 and the plane mode, the Intra16x16 DC Hadamard, per-macroblock
+ * QP, entropy coding. */
+#define DOVE_VCODEC_INTRA16 1
+#define DOVE_VCODEC_QPEL 2
+#define DOVE_VCODEC_DEBLOCK 4
+size_t dove_vcodec_tools_workspace_bytes(int n, int h, int w, int gop, int tools);
+int dove_vcodec_roundtrip_tools(const float* x, int n, int h, int w, long long bitrate, int gop, int tools, void* ws, size_t ws_bytes,
+                                unsigned char* out, int* qp_out, long long* bits_out, void* stream);
+
 /* The stitch of ref :712-720 for one piece: the box `valid` (piece coordinates) of piece [3][f][h][w] is copied to the box of the same size at
  * (out_t0, out_h0, out_w0) of chunk [3][f_chunk][Hs][Ws]; both bf16, contiguous.  One launch, no write counts; 16-byte loads and stores when
  * both boxes allow (the box width, every row / frame / channel stride of both arrays and both box origins multiples of 8 elements, i.e.

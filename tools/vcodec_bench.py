@@ -9,9 +9,13 @@ The search is set against its LDS traffic: per macroblock and candidate wave 16 
 (10 LDS cycles) plus the block row as a quarter of a ds_read_b128 per unrolled row (4 cycles), four waves per macroblock: 896 LDS cycles,
 on 256 CUs at 2.4 GHz.
 
+``--tools`` times the call with an H.264 tool set (names of ops.VCODEC_TOOLS, or ``all``): quarter-sample refinement after every search, one
+launch per macroblock anti-diagonal of every I frame, and two edge passes per frame, in each of the 7 passes.  The motion share is the
+integer search alone either way.
+
 hipEvents around CALLS calls after warm-up (docs/measurement.md).  Prints one JSON line per size.
 
-    python tools/vcodec_bench.py [--frames 16 --gop 8 --sizes 180x320 720x1280 --bitrate 30000 --calls 5]"""
+    python tools/vcodec_bench.py [--frames 16 --gop 8 --sizes 180x320 720x1280 --bitrate 30000 --calls 5 --tools all]"""
 import argparse
 import json
 import os
@@ -48,20 +52,20 @@ def clip(frames, h, w):
     return (fr + torch.randn(fr.shape, device="cuda", generator=g) * 3).contiguous()
 
 
-def bench(frames, h, w, gop, bitrate, calls):
+def bench(frames, h, w, gop, bitrate, calls, tools=()):
     from dove_amd import ops
     x = clip(frames, h, w)
     groups = -(-frames // gop)
     searches = QP_PASSES * (min(gop, frames) - 1)
-    out, qp, bits = ops.vcodec_roundtrip(x, bitrate, gop, want_stats=True)
-    total = time_ms(lambda: ops.vcodec_roundtrip(x, bitrate, gop), calls)
+    out, qp, bits = ops.vcodec_roundtrip(x, bitrate, gop, want_stats=True, tools=tools)
+    total = time_ms(lambda: ops.vcodec_roundtrip(x, bitrate, gop, tools=tools), calls)
     ph, pw = -(-h // 16) * 16, -(-w // 16) * 16
     luma = torch.nn.functional.pad(x[:groups + 1, :, :, 1].clamp(0, 255), (0, pw - w, 0, ph - h), mode="replicate").to(torch.uint8).contiguous()
     one = time_ms(lambda: ops.motion_search_u8(luma[1:], luma[:-1]), calls * 10)
     motion = one * searches
     mbs = (ph // 16) * (pw // 16) * groups * searches
     floor = mbs * LDS_CYCLES_PER_MB / (CUS * CLOCK) * 1e3
-    return {"clip": [frames, h, w, 3], "gop": gop, "bitrate": bitrate, "calls": calls, "qp": qp.cpu().tolist(), "bits": bits.cpu().tolist(),
+    return {"clip": [frames, h, w, 3], "gop": gop, "bitrate": bitrate, "tools": list(tools), "calls": calls, "qp": qp.cpu().tolist(), "bits": bits.cpu().tolist(),
             "total_ms": round(total, 3), "motion_ms": round(motion, 3), "rest_ms": round(total - motion, 3),
             "motion_launches": searches, "motion_launch_us": round(one * 1e3, 2), "motion_lds_floor_ms": round(floor, 3),
             "motion_x_floor": round(motion / floor, 1)}
@@ -74,11 +78,13 @@ def main(argv=None):
     ap.add_argument("--sizes", type=str, nargs="+", default=["180x320", "720x1280"])
     ap.add_argument("--bitrate", type=int, default=30000)
     ap.add_argument("--calls", type=int, default=5)
+    ap.add_argument("--tools", type=str, nargs="*", default=[], help="H.264 tools of the call: intra16 qpel deblock, or all")
     args = ap.parse_args(argv)
+    tools = ["intra16", "qpel", "deblock"] if args.tools == ["all"] else args.tools
     results = []
     for size in args.sizes:
         h, w = (int(v) for v in size.lower().split("x"))
-        results.append(bench(args.frames, h, w, args.gop, args.bitrate, args.calls))
+        results.append(bench(args.frames, h, w, args.gop, args.bitrate, args.calls, tools))
         print(json.dumps(results[-1]))
     return results
 
