@@ -144,7 +144,9 @@ def conv_out_gather(p, Cc, bias, dtype, scale=1.0, shift=0.0, lo=-math.inf, hi=m
         for dx in range(3):
             k = (dy * 3 + dx) * Cc
             acc += pp[:, k:k + Cc, dy:dy + H, dx:dx + W]
-    v = (acc + bias.float().view(1, Cc, 1, 1)).to(BF).float()
+    if bias is not None:                                                   # the kernel takes a null bias
+        acc = acc + bias.float().view(1, Cc, 1, 1)
+    v = acc.to(BF).float()
     return (v * scale + shift).clamp(lo, hi).permute(1, 0, 2, 3).contiguous().to(dtype)
 
 
