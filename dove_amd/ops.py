@@ -1605,3 +1605,147 @@ def musiq_score(features: torch.Tensor, w: torch.Tensor, b: torch.Tensor) -> tor
         L.check(L.load().dove_musiq_score(L.ptr(features), features.stride(0), L.ptr(w), L.ptr(b), N, D, w.shape[0], L.ptr(out), L.stream_ptr()),
                 "dove_musiq_score")
     return out
+
+
+# ---- FasterVQA / FAST-VQA (csrc/swin3d.hip): the fragment gather, 3-D windows, patch merging, window attention and the fp64 head ----------
+def _int3(values, what: str) -> "C.Array":
+    if len(values) != 3:
+        raise ValueError(f"{what} must have three entries, got {tuple(values)}")
+    return (C.c_int * 3)(*(int(v) for v in values))
+
+
+def vqa_fragments_f32(clip: torch.Tensor, frames: torch.Tensor, offsets: torch.Tensor, fragment, mean, std, cols: bool = False) -> torch.Tensor:
+    """clip: an [F,3,H,W] view (uint8, or float32 / bfloat16 in [0,1]; any strides, no copy), ``frames`` int32 [T] and ``offsets`` int32
+    [gh,gw,t_groups,2] (row, column of each fragment's top-left source pixel) on the device, ``fragment`` = (fh, fw) -> float32
+    [T,gh fh,gw fw,3]: (X - mean) / std in fp64, rounded once, X the uint8 value or 255 v.  ``cols``: the same values as the patch
+    embedding's GEMM rows, float32 [T/2,gh fh/4,gw fw/4,96] (csrc/swin3d.hip)."""
+    if clip.dim() != 4 or clip.shape[1] != 3 or not clip.is_cuda:
+        raise ValueError(f"vqa_fragments_f32: need an [F,3,H,W] view on the HIP device, got {tuple(clip.shape)} on {clip.device}")
+    _strided_on_device("vqa_fragments_f32", clip)
+    L.require_cuda(frames, offsets)
+    if frames.dtype != torch.int32 or frames.dim() != 1 or offsets.dtype != torch.int32 or offsets.dim() != 4 or offsets.shape[3] != 2:
+        raise ValueError("vqa_fragments_f32: frames must be int32 [T] and offsets int32 [gh,gw,t_groups,2]")
+    T, (gh, gw, tg, _), (fh, fw) = frames.shape[0], offsets.shape, fragment
+    if T == 0 or tg == 0 or T % tg:
+        raise ValueError(f"vqa_fragments_f32: {T} frames do not split into {tg} temporal groups")
+    Hc, Wc = gh * fh, gw * fw
+    if cols and (T % 2 or Hc % 4 or Wc % 4):
+        raise ValueError(f"vqa_fragments_f32: the patch rows need an even T and canvas sides that are multiples of 4, got {T} x {Hc} x {Wc}")
+    out = torch.empty((T // 2, Hc // 4, Wc // 4, 96) if cols else (T, Hc, Wc, 3), dtype=torch.float32, device=clip.device)
+    v = _image_view(clip)
+    L.check(L.load().dove_vqa_fragments_f32(C.byref(v), clip.shape[0], clip.shape[2], clip.shape[3], L.ptr(frames), T, L.ptr(offsets), gh, gw,
+                                            fh, fw, tg, (C.c_double * 3)(*map(float, mean)), (C.c_double * 3)(*map(float, std)), int(bool(cols)),
+                                            L.ptr(out), L.stream_ptr()), "dove_vqa_fragments_f32")
+    return out
+
+
+def _token_map(x: torch.Tensor, what: str):
+    L.require_cuda(x)
+    if x.dtype != torch.float32 or x.dim() != 5 or x.shape[4] % 4 or x.numel() == 0:
+        raise ValueError(f"{what}: x {tuple(x.shape)} {x.dtype} must be contiguous float32 [B,D,H,W,C] with C a multiple of 4")
+    return x.shape
+
+
+def swin3d_padded(dims, window):
+    """(padded dims, window count, window length) of a D x H x W map cut into ``window``-sized windows."""
+    padded = tuple(-(-d // w) * w for d, w in zip(dims, window))
+    return padded, (padded[0] // window[0]) * (padded[1] // window[1]) * (padded[2] // window[2]), window[0] * window[1] * window[2]
+
+
+def swin3d_window_gather_f32(x: torch.Tensor, window, shift=(0, 0, 0)) -> torch.Tensor:
+    """Token map float32 [B,D,H,W,C] -> windows float32 [B nW,N,C]: zero pad to multiples of ``window``, roll by -``shift``, partition
+    (one pass; padded slots read 0).  ``window`` and ``shift`` are the clamped ones (0 <= shift < window)."""
+    B, D, H, W, Cc = _token_map(x, "swin3d_window_gather_f32")
+    _, nW, N = swin3d_padded((D, H, W), window)
+    out = torch.empty(B * nW, N, Cc, dtype=torch.float32, device=x.device)
+    L.check(L.load().dove_swin3d_window_gather_f32(L.ptr(x), B, _int3((D, H, W), "dims"), Cc, _int3(window, "window"), _int3(shift, "shift"),
+                                                   L.ptr(out), L.stream_ptr()), "dove_swin3d_window_gather_f32")
+    return out
+
+
+def swin3d_window_scatter_f32(windows: torch.Tensor, shortcut: torch.Tensor, window, shift=(0, 0, 0), out: torch.Tensor | None = None):
+    """The inverse of ``swin3d_window_gather_f32`` plus the shortcut: windows float32 [B nW,N,C] and shortcut [B,D,H,W,C] -> shortcut +
+    (windows merged, rolled back, cropped).  ``out`` may be ``shortcut``."""
+    B, D, H, W, Cc = _token_map(shortcut, "swin3d_window_scatter_f32")
+    L.require_cuda(windows)
+    _, nW, N = swin3d_padded((D, H, W), window)
+    if windows.dtype != torch.float32 or tuple(windows.shape) != (B * nW, N, Cc):
+        raise ValueError(f"swin3d_window_scatter_f32: windows {tuple(windows.shape)} {windows.dtype} must be float32 {(B * nW, N, Cc)}")
+    if out is None:
+        out = torch.empty_like(shortcut)
+    elif out.shape != shortcut.shape or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("swin3d_window_scatter_f32: out must be contiguous float32 of the shortcut's shape")
+    L.check(L.load().dove_swin3d_window_scatter_f32(L.ptr(windows), L.ptr(shortcut), B, _int3((D, H, W), "dims"), Cc, _int3(window, "window"),
+                                                    _int3(shift, "shift"), L.ptr(out), L.stream_ptr()), "dove_swin3d_window_scatter_f32")
+    return out
+
+
+def swin3d_patch_merge_f32(x: torch.Tensor) -> torch.Tensor:
+    """Token map float32 [B,D,H,W,C] -> [B,D,ceil(H/2),ceil(W/2),4 C]: the 2 x 2 neighbours (0,0), (1,0), (0,1), (1,1) side by side, odd
+    H or W zero-padded."""
+    B, D, H, W, Cc = _token_map(x, "swin3d_patch_merge_f32")
+    out = torch.empty(B, D, (H + 1) // 2, (W + 1) // 2, 4 * Cc, dtype=torch.float32, device=x.device)
+    L.check(L.load().dove_swin3d_patch_merge_f32(L.ptr(x), B * D, H, W, Cc, L.ptr(out), L.stream_ptr()), "dove_swin3d_patch_merge_f32")
+    return out
+
+
+def swin3d_attention_tiles() -> tuple:
+    """(query tile, key tile, longest window) of ``swin3d_window_attention_f32``'s kernel; needs no device."""
+    q, kv, mx = C.c_int(0), C.c_int(0), C.c_int(0)
+    L.load().dove_swin3d_attention_tiles(C.byref(q), C.byref(kv), C.byref(mx))
+    return q.value, kv.value, mx.value
+
+
+def swin3d_window_attention_f32(qkv: torch.Tensor, heads: int, table: torch.Tensor, index: torch.Tensor, *, scale: float | None = None,
+                                table_b: torch.Tensor | None = None, frag: torch.Tensor | None = None,
+                                region: torch.Tensor | None = None) -> torch.Tensor:
+    """qkv float32 [W,N,3 heads 32] (q, k, v side by side), ``table`` float32 [R,heads], ``index`` int32 [N,N] -> float32 [W,N,heads 32]:
+    softmax(scale q k^T + table[index] + mask) v per window and head on the fp32 MFMA (csrc/swin3d.hip).  ``region`` int32 [w,N] (w divides
+    W: the windows of one sample): -100 between tokens of different ids.  ``table_b`` with ``frag`` int32 [w,N]: the bias of token pairs
+    whose ids differ comes from ``table_b``.  ``scale`` defaults to 1 / sqrt(32)."""
+    L.require_cuda(qkv, table, index, table_b, frag, region)
+    if qkv.dtype != torch.float32 or qkv.dim() != 3 or qkv.shape[2] != 3 * heads * 32 or qkv.numel() == 0:
+        raise ValueError(f"swin3d_window_attention_f32: qkv {tuple(qkv.shape)} {qkv.dtype} must be float32 [W,N,{3 * heads * 32}] for {heads} heads of 32")
+    Wn, N, _ = qkv.shape
+    if N > swin3d_attention_tiles()[2]:
+        raise ValueError(f"swin3d_window_attention_f32: a window of {N} tokens is longer than the kernel's {swin3d_attention_tiles()[2]}")
+    tabs = [table] + ([table_b] if table_b is not None else [])
+    if any(t.dtype != torch.float32 or t.dim() != 2 or t.shape != table.shape or t.shape[1] != heads for t in tabs):
+        raise ValueError(f"swin3d_window_attention_f32: the bias tables must be float32 [R,{heads}] of one shape")
+    if index.dtype != torch.int32 or tuple(index.shape) != (N, N):
+        raise ValueError(f"swin3d_window_attention_f32: index must be int32 {(N, N)}, got {index.dtype} {tuple(index.shape)}")
+    if table_b is not None and frag is None:
+        raise ValueError("swin3d_window_attention_f32: a second table needs the fragment ids")
+    idw = 1
+    for name, t in (("frag", frag), ("region", region)):
+        if t is None:
+            continue
+        if t.dtype != torch.int32 or t.dim() != 2 or t.shape[1] != N or t.shape[0] == 0 or Wn % t.shape[0]:
+            raise ValueError(f"swin3d_window_attention_f32: {name} must be int32 [w,{N}] with w dividing {Wn}, got {t.dtype} {tuple(t.shape)}")
+        idw = t.shape[0]
+    if frag is not None and region is not None and frag.shape != region.shape:
+        raise ValueError("swin3d_window_attention_f32: frag and region must have one shape")
+    D = heads * 32
+    out = torch.empty(Wn, N, D, dtype=torch.float32, device=qkv.device)
+    L.check(L.load().dove_swin3d_window_attention_f32(
+        L.ptr(qkv), C.c_void_p(qkv.data_ptr() + 4 * D), C.c_void_p(qkv.data_ptr() + 8 * D), 3 * D, Wn, N, heads,
+        1.0 / math.sqrt(32.0) if scale is None else float(scale), L.ptr(table), L.ptr(table_b), table.shape[0], L.ptr(index), L.ptr(frag),
+        L.ptr(region), idw, L.ptr(out), D, L.stream_ptr()), "dove_swin3d_window_attention_f32")
+    return out
+
+
+def vqa_head_f64(features: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor) -> torch.Tensor:
+    """features float32 [clips,tokens,D], fc_hid weight [hid,D] and bias [hid], fc_last weight [hid] and bias [1] -> float64 [clips]: the
+    mean over tokens of fc_last(gelu(fc_hid(f))) in fp64 with fixed-order sums."""
+    L.require_cuda(features, w1, b1, w2, b2)
+    if features.dtype != torch.float32 or features.dim() != 3 or features.numel() == 0:
+        raise ValueError(f"vqa_head_f64: features {tuple(features.shape)} {features.dtype} must be float32 [clips,tokens,D]")
+    n, T, D = features.shape
+    hid = w1.shape[0]
+    if any(t.dtype != torch.float32 for t in (w1, b1, w2, b2)) or tuple(w1.shape) != (hid, D) or b1.numel() != hid or w2.numel() != hid or \
+            b2.numel() != 1 or hid > 256:
+        raise ValueError(f"vqa_head_f64: need float32 w1 [hid,{D}], b1 [hid], w2 [hid], b2 [1] with hid <= 256")
+    out = torch.empty(n, dtype=torch.float64, device=features.device)
+    L.check(L.load().dove_vqa_head_f64(L.ptr(features), D, n, T, D, L.ptr(w1), L.ptr(b1), hid, L.ptr(w2), L.ptr(b2), L.ptr(out), L.stream_ptr()),
+            "dove_vqa_head_f64")
+    return out

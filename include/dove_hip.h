@@ -927,6 +927,48 @@ void dove_mha_f32_tiles(int* q_tile, int* kv_tile);
 int dove_gelu_f32(const float* x, long long count, float* out, void* stream);
 int dove_musiq_score(const float* features, long long ld, const float* w, const float* b, int n, int dim, int k, double* out, void* stream);
 
+/* FasterVQA / FAST-VQA (csrc/swin3d.hip; tests/fastvqa_ref.py is the definition): what a Video Swin-T with gated relative
+ * position bias needs beside dove_resnet_conv_f32's 1 x 1 walk (every Linear, tokens as pixels), dove_layernorm_f32 and dove_gelu_f32.  Token
+ * maps are channels-last fp32 [b][d][h][w][c], dense; no atomics, identical bits on repetition, a sample's result independent of the batch.
+ * None of these needs a workspace.
+ *   vqa_fragments_f32: clip is frames_in frames [3][h][w] (f32 / bf16 in [0,1], or u8; any strides).  frames [t] int32 and offsets [gh][gw]
+ *     [t_groups][2] int32 (row, column: the top-left source pixel of a fragment) are on the device; mean[3], std[3] on the host.  Output pixel
+ *     (t, y, x) of the [t][gh fh][gw fw] canvas is pixel offsets[y / fh][x / fw][t / (t / t_groups)] + (y % fh, x % fw) of frame frames[t]; a
+ *     coordinate or frame index outside the clip is clamped into it.  Value (X - mean_c) / std_c evaluated in fp64 and rounded once, with X the u8
+ *     value itself, or 255.0 v otherwise.  cols == 0: out is the canvas [t][gh fh][gw fw][3].  cols != 0 (t even, canvas sides multiples of 4): out
+ *     is [t / 2][gh fh / 4][gw fw / 4][96], the rows of the (2, 4, 4) stride-(2, 4, 4) patch embedding's GEMM, column c 32 + (t % 2) 16 + (y % 4) 4
+ *     + x % 4 (a Conv3d weight [out][3][2][4][4] flattened); the embedding is then one k-ordered fp32 FMA chain of 96 terms per output.
+ *   swin3d_window_gather_f32: x [b][dims] [c] -> out [b nW][N][c], N = window[0] window[1] window[2], nW the window count of the map padded to
+ *     multiples of the window.  Slot n of window a is padded position p = a window + n per axis (both row-major over d, h, w) and holds map
+ *     position (p + shift) % padded, torch.roll by -shift, or 0 where that is in the pad.  0 <= shift < window; c a multiple of 4.  The caller
+ *     applies Video Swin's rule that an axis no longer than its window uses its own length as the window and shift 0.
+ *   swin3d_window_scatter_f32: the inverse on the unpadded map, out = shortcut + windows; out may be shortcut.
+ *   swin3d_patch_merge_f32: x [maps][h][w][c] -> out [maps][ceil(h / 2)][ceil(w / 2)][4 c]: chunk j of an output pixel is input pixel (2 h2 +
+ *     (j & 1), 2 w2 + (j >> 1)), Swin's order (0,0), (1,0), (0,1), (1,1), or 0 outside the map.
+ *   swin3d_window_attention_f32: q, k, v: rows of stride ld, `windows` windows of n rows each, head h in columns [32 h, 32 h + 32) (slices of
+ *     one QKV buffer); out likewise with stride ldo.  Per window and head, in fp32 on v_mfma_f32_32x32x2_f32 with K and V of the window in LDS:
+ *     s = (q . k) scale + T[index[query][key]][h] + (region[query] != region[key] ? -100 : 0), out = softmax(s) v.  index [n][n] int32 into
+ *     tables of [table_rows][heads] (an entry outside [0, table_rows) is clamped); T = table_b where it is given and frag[query] != frag[key], else
+ *     table_a.  frag and region are [id_windows][n] int32 and window a uses row a % id_windows (id_windows: the windows of one sample); either
+ *     may be NULL (no gate / no mask).  The softmax is two-pass: the true row maximum over all keys first, then expf(s - max) (accurate expf), row
+ *     sums in key order, no n x n matrix stored.  1 <= n <= 392 (dove_swin3d_attention_tiles reports the 32 x 32 tile and this limit); ld, ldo
+ *     multiples of 4 and 16-byte aligned pointers.  The head's column of each table is kept in LDS beside K and V: 260 bytes per 32 tokens
+ *     (rounded up) of n plus 4 bytes per table row must fit 160 KiB (n = 392 with two tables of 2535 rows needs 129 KiB).
+ *   vqa_head_f64: features [clips][tokens] rows of dim at stride ld; w1 [hidden][dim], b1 [hidden], w2 [hidden], b2 [1] fp32 -> out[clips] fp64:
+ *     the mean over a clip's tokens of w2 . gelu(w1 f + b1) + b2 in fp64 (exact erf), every sum in a fixed order.  hidden <= 256. */
+int dove_vqa_fragments_f32(const dove_image_view* clip, int frames_in, int h, int w, const int* frames, int t, const int* offsets, int gh, int gw,
+                           int fh, int fw, int t_groups, const double* mean, const double* std, int cols, float* out, void* stream);
+int dove_swin3d_window_gather_f32(const float* x, int b, const int* dims, int c, const int* window, const int* shift, float* out, void* stream);
+int dove_swin3d_window_scatter_f32(const float* windows, const float* shortcut, int b, const int* dims, int c, const int* window,
+                                   const int* shift, float* out, void* stream);
+int dove_swin3d_patch_merge_f32(const float* x, long long maps, int h, int w, int c, float* out, void* stream);
+void dove_swin3d_attention_tiles(int* q_tile, int* kv_tile, int* max_n);
+int dove_swin3d_window_attention_f32(const float* q, const float* k, const float* v, long long ld, long long windows, int n, int heads,
+                                     float scale, const float* table_a, const float* table_b, int table_rows, const int* index, const int* frag,
+                                     const int* region, int id_windows, float* out, long long ldo, void* stream);
+int dove_vqa_head_f64(const float* features, long long ld, int clips, int tokens, int dim, const float* w1, const float* b1, int hidden,
+                      const float* w2, const float* b2, double* out, void* stream);
+
 /* ---- PNG encoder (csrc/png.hip; tests/png_ref.py is the bit-exact definition of the filtered stream) ----
  * png_encode: img is a strided [n,channels,h,w] view as above (channels 3 = RGB, 1 = grey; u8 as it is, f32 / bf16 quantised as
  *   dove_postprocess_u8 does, trunc(clamp(255 x, 0, 255))).  Frame i becomes a complete 8-bit, non-interlaced PNG file at

@@ -51,6 +51,8 @@ class Stages:
     NAMES = ("musiq_patches_f32", "convnet_conv_f32", "resnet_conv_f32", "linear_f32", "musiq_groupnorm_f32", "layernorm_f32", "musiq_embed_f32",
              "mha_f32", "gelu_f32", "musiq_score")
 
+    label, flops = staticmethod(_label), staticmethod(_flops)            # a subclass for another network replaces NAMES and these two
+
     def __init__(self, ops):
         self.ops, self.events, self.saved, self.depth = ops, [], {}, 0
 
@@ -66,7 +68,7 @@ class Stages:
             finally:
                 e.record()
                 self.depth -= 1
-                self.events.append((_label(name, a), _flops(name, a), s, e))
+                self.events.append((self.label(name, a), self.flops(name, a), s, e))
         return timed
 
     def __enter__(self):
