@@ -33,9 +33,8 @@ import numpy as np
 import torch
 
 from . import iqa, ops
-from .flow import pack_conv_weight
 from .iqa import ACTIVATION_BUDGET, FLOAT32_DTYPES, GpuMetric, find_file, find_first, for_groups, score_folder
-from .percep import _checked, _strip, _Weights
+from .netweights import Weights, bn_affine, checked, fan_in_normal, he_normal, pack_conv_weight, random_tensors, strip
 
 CLIP_MEAN, CLIP_STD = (0.48145466, 0.4578275, 0.40821073), (0.26862954, 0.26130258, 0.27577711)
 LAYERS, PLANES, EXPANSION = (3, 4, 6, 3), (64, 128, 256, 512), 4
@@ -125,22 +124,20 @@ def random_clipiqa_state(seed: int):
     perturbation of 0.4 of its length, so that a pair's logits differ by a unit or two and no pair softmax saturates.  TEXT_DRAW, the
     third key of that generator, was chosen among 60 so that the scores of the tests' images (seed 31) also differ between noise levels
     by several 1e-3 under the fp64 restatement; tests/test_clipiqa_cpu.py asserts both."""
-    sd = {}
-    for name, shape in visual_param_shapes().items():
-        rng = np.random.default_rng([int(seed), zlib.crc32(f"clipiqa.{name}".encode())])
+    def rule(name, shape, rng):
         if name == "logit_scale":
-            v = np.asarray(math.log(100.0))
-        elif len(shape) == 4:
-            v = rng.standard_normal(shape) * math.sqrt(2.0 / (shape[1] * shape[2] * shape[3]))
-        elif len(shape) == 2:
-            v = rng.standard_normal(shape) / math.sqrt(shape[1])
-        elif name.endswith("running_var"):
-            v = rng.uniform(0.5, 1.5, shape)
-        elif name.endswith(".weight"):
-            v = rng.uniform(0.1, 0.3, shape) if ".bn3." in name else rng.uniform(0.5, 1.5, shape)
-        else:
-            v = 0.05 * rng.standard_normal(shape)
-        sd[name] = torch.from_numpy(np.asarray(v, dtype=np.float32))
+            return math.log(100.0)
+        if len(shape) == 4:
+            return he_normal(rng, shape)
+        if len(shape) == 2:
+            return fan_in_normal(rng, shape)
+        if name.endswith("running_var"):
+            return rng.uniform(0.5, 1.5, shape)
+        if name.endswith(".weight"):
+            return rng.uniform(0.1, 0.3, shape) if ".bn3." in name else rng.uniform(0.5, 1.5, shape)
+        return 0.05 * rng.standard_normal(shape)
+
+    sd = random_tensors(visual_param_shapes(), seed, lambda name: f"clipiqa.{name}", rule)
     rng = np.random.default_rng([int(seed), zlib.crc32(b"clipiqa.text"), TEXT_DRAW])
     pos = rng.standard_normal((len(PROMPTS), OUTPUT_DIM))
     neg = pos + 0.4 * rng.standard_normal(pos.shape)
@@ -150,8 +147,8 @@ def random_clipiqa_state(seed: int):
 
 def fold_bn(w: torch.Tensor, gamma, beta, mean, var, eps: float = BN_EPS):
     """conv weight [Cout,Cin,kh,kw] and eval-mode BatchNorm -> (weight, bias) in fp64: s = gamma / sqrt(var + eps), w s, beta - mean s."""
-    s = gamma.double() / torch.sqrt(var.double() + eps)
-    return w.double() * s[:, None, None, None], beta.double() - mean.double() * s
+    s, shift = bn_affine(gamma, beta, mean, var, eps)
+    return w.double() * s[:, None, None, None], shift
 
 
 def _folded(sd: dict, conv: str, bn: str):
@@ -171,12 +168,12 @@ _load_sd = functools.partial(iqa.load_state_dict, torchscript=True)
 
 
 @dataclass
-class ClipIqaWeights(_Weights):
+class ClipIqaWeights(Weights):
+    convs: dict = field(default_factory=dict)       # conv name -> (w [kh,kw,cin,cout] with its BatchNorm folded in, bias)
     attn: list = field(default_factory=list)        # wq, bq, wk, bk, wv, bv, wc, bc (float32, [out,in] weights)
     text: list = field(default_factory=list)        # [features float64 [2P,1024], L2-normalised]
     logit_scale: float = 100.0                      # exp of CLIP's parameter
     prompts: tuple = ()
-    _TENSOR_LISTS = ("attn", "text")
 
     @classmethod
     def from_state_dict(cls, sd: dict, text=None) -> "ClipIqaWeights":
@@ -184,7 +181,7 @@ class ClipIqaWeights(_Weights):
         if text is None:
             raise ValueError("CLIP-IQA needs the text features of its prompts: pass the contents of clipiqa_text.npz, or make them with "
                              "`python -m dove_amd.clipiqa text --model RN50.pt --vocab bpe_simple_vocab_16e6.txt.gz --out DIR/clipiqa_text.npz`")
-        sd = _checked(_strip(sd), visual_param_shapes(), "CLIP RN50 checkpoint")
+        sd = checked(strip(sd), visual_param_shapes(), "CLIP RN50 checkpoint")
         convs = {f"visual.{conv}": _folded(sd, f"visual.{conv}", f"visual.{bn}") for conv, bn, _, _, _ in STEM}
         for p, _, _, _, down in _blocks():
             for i in (1, 2, 3):
@@ -199,7 +196,7 @@ class ClipIqaWeights(_Weights):
     @classmethod
     def load(cls, directory: str) -> "ClipIqaWeights":
         """From a ``--metric_weights`` directory: ``RN50*.pt`` / ``RN50*.pth``, and ``clipiqa_text*.npz`` or CLIP's vocabulary file."""
-        sd = _strip(_load_sd(find_file(directory, FILE_PATTERNS["model"])))
+        sd = strip(_load_sd(find_file(directory, FILE_PATTERNS["model"])))
         npz, vocab = find_first(directory, FILE_PATTERNS["text"]), find_first(directory, FILE_PATTERNS["vocab"])
         if npz is not None:
             with np.load(npz, allow_pickle=False) as z:
@@ -385,7 +382,7 @@ def encode_text(sd: dict, tokens: torch.Tensor, dtype=torch.float64) -> torch.Te
 
 def text_features(sd: dict, vocab_path: str, prompts=None) -> torch.Tensor:
     """The fp64 text features [2P,1024] (not normalised) of the prompt pairs under the checkpoint's text tower."""
-    sd = _checked(_strip(sd), text_param_shapes(), "CLIP RN50 checkpoint (text tower)")
+    sd = checked(strip(sd), text_param_shapes(), "CLIP RN50 checkpoint (text tower)")
     flat = [p for pair in (PROMPTS if prompts is None else prompts) for p in pair]
     return encode_text(sd, Tokenizer.from_file(vocab_path)(flat))
 
@@ -410,7 +407,7 @@ def main(argv=None):
         pairs = [tuple(p.split("|")) for p in args.prompts.split(";") if p.strip()] or list(PROMPTS)
         if any(len(p) != 2 for p in pairs):
             raise ValueError(f"--prompts {args.prompts!r}: every pair is 'positive|negative'")
-        sd = _strip(_load_sd(args.model))
+        sd = strip(_load_sd(args.model))
         feats = text_features(sd, args.vocab, pairs)
         save_text(args.out, feats.numpy(), [p for pair in pairs for p in pair], float(sd["logit_scale"]))
         print(f"text features of {len(pairs)} prompt pairs -> {args.out}")

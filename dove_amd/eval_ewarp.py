@@ -10,31 +10,17 @@ defined in dove_amd.flow (the reference does not ship its ``ewarp`` module)."""
 from __future__ import annotations
 
 import argparse
-import json
-import math
 import os
 
-from . import prepost
+from .iqa import list_clips, process_clips, summarize as _summarize  # noqa: F401  (list_clips: eval_fastvqa and tests read it here)
 
 METRIC = "warping_error"
 OUT_NAME = "metrics_ewarp.json"
 
 
-def list_clips(pred_root: str) -> dict:
-    """{os.path.splitext stem: path} of the folders, ``.npy`` and ``.y4m`` entries of ``pred_root``."""
-    clips = {}
-    for item in sorted(os.listdir(pred_root)):
-        path = os.path.join(pred_root, item)
-        if os.path.isdir(path) or item.lower().endswith((".npy", ".y4m")):
-            clips[os.path.splitext(item)[0]] = path
-    return clips
-
-
 def summarize(results: dict) -> dict:
     """per_sample, the average of the (rounded) per-sample values that are numbers, count."""
-    vals = [v[METRIC] for v in results.values() if not math.isnan(v[METRIC])]
-    average = {METRIC: round(sum(vals) / len(vals), 4) if vals else float("nan")} if results else {}
-    return {"per_sample": results, "average": average, "count": len(results)}
+    return _summarize(results, (METRIC,))
 
 
 def process(pred_root: str, out_path: str, model: str, iters: int = 20, clip_error_fn=None) -> dict:
@@ -49,28 +35,17 @@ def process(pred_root: str, out_path: str, model: str, iters: int = 20, clip_err
             raise FileNotFoundError(f"--model {model}: the RAFT checkpoint (raft-things.pth) is not shipped; pass your own file")
         weights = flow.RaftWeights.load(model)
         clip_error_fn = lambda frames: flow.warping_error(frames, weights, iters)
-    results = {}
-    for name, path in list_clips(pred_root).items():
-        try:
-            frames = prepost.load_frames(path)
-            if frames.shape[0] < 2:
-                print(f"Skipping {name}: a clip needs at least 2 frames.")
-                continue
-            r = clip_error_fn(frames)
-            if r.get("pairs_without_valid_pixels"):
-                print(f"{name}: {r['pairs_without_valid_pixels']} of {r['pairs']} pairs have no valid pixel")
-            results[name] = {METRIC: round(r[METRIC], 4)}
-        except Exception as e:
-            print(f"Error processing {name}: {e}")
-    output = summarize(results)
-    print(f"\nProcessed {output['count']} samples.")
-    print(f"Average score: {output['average']}")
-    os.makedirs(out_path, exist_ok=True)
-    path = os.path.join(out_path, OUT_NAME)
-    with open(path, "w") as f:
-        json.dump(output, f, indent=2)
-    print(f"Results saved to: {path}")
-    return output
+
+    def clip(name, frames):
+        if frames.shape[0] < 2:
+            print(f"Skipping {name}: a clip needs at least 2 frames.")
+            return None
+        r = clip_error_fn(frames)
+        if r.get("pairs_without_valid_pixels"):
+            print(f"{name}: {r['pairs_without_valid_pixels']} of {r['pairs']} pairs have no valid pixel")
+        return {METRIC: round(r[METRIC], 4)}
+
+    return process_clips(pred_root, out_path, OUT_NAME, (METRIC,), clip)
 
 
 def build_parser() -> argparse.ArgumentParser:

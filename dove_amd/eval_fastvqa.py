@@ -10,12 +10,9 @@ values too, hence the two override flags."""
 from __future__ import annotations
 
 import argparse
-import json
-import math
 import os
 
-from . import prepost
-from .eval_ewarp import list_clips
+from .iqa import list_clips, process_clips, summarize as _summarize  # noqa: F401  (list_clips: tests read it here)
 
 METRIC, RAW = "fastervqa", "fastervqa_raw"
 OUT_NAME = "metrics_fastervqa.json"
@@ -23,12 +20,7 @@ OUT_NAME = "metrics_fastervqa.json"
 
 def summarize(results: dict) -> dict:
     """per_sample, the average of the (rounded) per-sample values, count."""
-    average = {}
-    for key in (METRIC, RAW):
-        vals = [v[key] for v in results.values() if not math.isnan(v[key])]
-        if results:
-            average[key] = round(sum(vals) / len(vals), 4) if vals else float("nan")
-    return {"per_sample": results, "average": average, "count": len(results)}
+    return _summarize(results, (METRIC, RAW))
 
 
 def make_score_fn(model: str, variant: str = "FasterVQA", seed: int = 42, rescale_mean=None, rescale_std=None):
@@ -51,22 +43,12 @@ def process(pred_root: str, out_path: str, model: str = "", variant: str = "Fast
     """``score_fn(frames_u8) -> (raw, rescaled)`` defaults to ``fastvqa.score_clip`` with the weights of ``model``."""
     if score_fn is None:
         score_fn = make_score_fn(model, variant, seed, rescale_mean, rescale_std)
-    results = {}
-    for name, path in list_clips(pred_root).items():
-        try:
-            raw, scaled = score_fn(prepost.load_frames(path))
-            results[name] = {METRIC: round(float(scaled), 4), RAW: round(float(raw), 4)}
-        except Exception as e:
-            print(f"Error processing {name}: {e}")
-    output = summarize(results)
-    print(f"\nProcessed {output['count']} samples.")
-    print(f"Average score: {output['average']}")
-    os.makedirs(out_path, exist_ok=True)
-    path = os.path.join(out_path, OUT_NAME)
-    with open(path, "w") as f:
-        json.dump(output, f, indent=2)
-    print(f"Results saved to: {path}")
-    return output
+
+    def clip(name, frames):
+        raw, scaled = score_fn(frames)
+        return {METRIC: round(float(scaled), 4), RAW: round(float(raw), 4)}
+
+    return process_clips(pred_root, out_path, OUT_NAME, (METRIC, RAW), clip)
 
 
 def build_parser() -> argparse.ArgumentParser:

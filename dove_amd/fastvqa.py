@@ -21,7 +21,6 @@ its global random streams.  The user supplies the checkpoint.  This module walks
 from __future__ import annotations
 
 import math
-import zlib
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -29,7 +28,7 @@ import torch
 
 from . import iqa, ops
 from .iqa import ACTIVATION_BUDGET, for_groups, load_state_dict
-from .percep import _checked, _strip
+from .netweights import Weights, checked, device_tables, fan_in_normal, nearest_index, pack_linear_weight, prenorm_mlp_f32, random_tensors, strip
 
 MEAN, STD = (123.675, 116.28, 103.53), (58.395, 57.12, 57.375)
 LN_EPS = 1e-5
@@ -159,11 +158,6 @@ def relative_index(window) -> np.ndarray:
     return (rel[..., 0] * (2 * wh - 1) + rel[..., 1]) * (2 * ww - 1) + rel[..., 2]
 
 
-def nearest_index(count: int, grid: int) -> np.ndarray:
-    """torch's nearest-neighbour F.interpolate of arange(grid) to ``count`` points: floor(i * (grid / count)) in float32, at most grid - 1."""
-    return np.minimum(np.floor(np.arange(count, dtype=np.float32) * (np.float32(grid) / np.float32(count))).astype(np.int64), grid - 1)
-
-
 _GEOMETRY = {}
 
 
@@ -194,13 +188,6 @@ def geometry(dims, window, fragments, shifted: bool) -> dict:
            "device": {}}
     _GEOMETRY[key] = geo
     return geo
-
-
-def _device_tables(geo: dict, device):
-    if device not in geo["device"]:
-        up = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(device)
-        geo["device"][device] = (up(geo["index"]), up(geo["frag"]), up(geo["region"]))
-    return geo["device"][device]
 
 
 # ------------------------------------------------------------------- weights -------------------------------------------------------------------
@@ -236,35 +223,27 @@ def random_state(cfg: VqaConfig, seed: int) -> dict:
     """Rule-generated state dict for tests and tools: matrices normal with std 1 / sqrt(fan-in), norm weights uniform in [0.5, 1.5],
     biases 0.05 * normal, bias tables normal with std 1 (so that the bias and the gate matter next to the scores).  Each tensor has its
     own generator keyed by (seed, name)."""
-    sd = {}
-    for name, shape in param_shapes(cfg).items():
-        rng = np.random.default_rng([int(seed), zlib.crc32(f"fastvqa.{name}".encode())])
+    def rule(name, shape, rng):
         if name.endswith("_bias_table"):
-            v = rng.standard_normal(shape)
-        elif len(shape) >= 2:
-            v = rng.standard_normal(shape) / math.sqrt(float(np.prod(shape[1:])))
-        elif name.endswith(".weight"):
-            v = rng.uniform(0.5, 1.5, shape)
-        else:
-            v = 0.05 * rng.standard_normal(shape)
-        sd[name] = torch.from_numpy(np.asarray(v, dtype=np.float32))
-    return sd
+            return rng.standard_normal(shape)
+        if len(shape) >= 2:
+            return fan_in_normal(rng, shape)
+        return rng.uniform(0.5, 1.5, shape) if name.endswith(".weight") else 0.05 * rng.standard_normal(shape)
+
+    return random_tensors(param_shapes(cfg), seed, lambda name: f"fastvqa.{name}", rule)
 
 
 @dataclass
-class VqaWeights:
+class VqaWeights(Weights):
     """``params``: every tensor by its published name without the backbone prefix; Linear weights transposed to the GEMM's [1,1,in,out]."""
     cfg: VqaConfig = field(default_factory=VqaConfig)
     params: dict = field(default_factory=dict)
-    device: torch.device = torch.device("cpu")
-    _copies: dict = field(default_factory=dict, repr=False)
 
     @classmethod
     def from_state_dict(cls, sd: dict, cfg: VqaConfig | str = "FasterVQA") -> "VqaWeights":
         cfg = preset(cfg) if isinstance(cfg, str) else cfg
-        sd = _checked(_strip(sd), param_shapes(cfg), f"{cfg.name} checkpoint")
+        sd = checked(strip(sd), param_shapes(cfg), f"{cfg.name} checkpoint")
         f32 = lambda t: t.detach().float().contiguous()
-        lin = lambda w: f32(w.detach().float().flatten(1).t())[None, None]                      # [out,in...] -> the 1 x 1 walk's [1,1,in,out]
         p = {}
         for name in param_shapes(cfg):
             short = name[len(PREFIX):] if name.startswith(PREFIX) else name
@@ -274,23 +253,13 @@ class VqaWeights:
             elif short == "vqa_head.fc_last.weight":
                 p[short] = f32(t.flatten())
             else:
-                p[short] = lin(t) if t.dim() >= 2 and not short.endswith("_bias_table") else f32(t)
+                p[short] = pack_linear_weight(t) if t.dim() >= 2 and not short.endswith("_bias_table") else f32(t)
         return cls(cfg=cfg, params=p)
 
     @classmethod
     def load(cls, path: str, cfg: VqaConfig | str = "FasterVQA") -> "VqaWeights":
         """From a checkpoint file in the published layout (a top-level ``state_dict`` is unwrapped)."""
         return cls.from_state_dict(load_state_dict(path), cfg)
-
-    def to(self, device):
-        device = torch.device(device)
-        if device.type == "cuda" and device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        if device == self.device:
-            return self
-        if device not in self._copies:
-            self._copies[device] = VqaWeights(cfg=self.cfg, params={n: t.to(device) for n, t in self.params.items()}, device=device)
-        return self._copies[device]
 
 
 # -------------------------------------------------------------------- walk --------------------------------------------------------------------
@@ -303,7 +272,7 @@ def block(W: VqaWeights, x: torch.Tensor, p: str, heads: int, shifted: bool, gat
     B, D, H, Wd, C = x.shape
     P = W.params
     geo = geometry((D, H, Wd), W.cfg.window, W.cfg.fragments, shifted)
-    index, frag, region = _device_tables(geo, x.device)
+    index, frag, region = device_tables(geo, x.device, ("index", "frag", "region"))
     rows = x.view(-1, C)
     h = _ln(W, p + ".norm1", rows)
     win = ops.swin3d_window_gather_f32(h.view(x.shape), geo["window"], geo["shift"])
@@ -316,10 +285,7 @@ def block(W: VqaWeights, x: torch.Tensor, p: str, heads: int, shifted: bool, gat
     del a
     ops.swin3d_window_scatter_f32(win, x, geo["window"], geo["shift"], out=x)
     del win
-    _ln(W, p + ".norm2", rows, out=h)
-    m = ops.linear_f32(h, P[p + ".mlp.fc1.weight"], P[p + ".mlp.fc1.bias"])
-    ops.gelu_f32(m, out=m)
-    ops.linear_f32(m, P[p + ".mlp.fc2.weight"], P[p + ".mlp.fc2.bias"], residual=rows, out=rows)
+    prenorm_mlp_f32(rows, h, P, p + ".norm2", p + ".mlp.fc1", p + ".mlp.fc2", LN_EPS)
     return x
 
 

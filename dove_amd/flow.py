@@ -12,8 +12,6 @@ error on the reference's own ``flow_warp`` and ``fbConsistencyCheck`` (INTEGRATI
 """
 from __future__ import annotations
 
-import math
-import zlib
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -21,6 +19,8 @@ import torch
 
 from . import lib as L
 from . import ops
+from .iqa import load_state_dict
+from .netweights import Weights, bn_affine, checked, he_normal, pack_conv_weight, random_tensors, strip     # flow.pack_conv_weight stays a name
 
 BN_EPS = 1e-5
 HDIM = CDIM = 128
@@ -82,36 +82,25 @@ def random_raft_state(seed: int) -> dict:
     """A rule-generated state dict of the basic model (tests and tools; a flow network that means nothing, with healthy magnitudes):
     one numpy generator per name; conv weights normal with std sqrt(2 / fan_in), conv biases 0.05 * normal, BatchNorm weight and
     running_var uniform in [0.5, 1.5], BatchNorm bias and running_mean 0.1 * normal.  ``downsample.1`` repeats ``norm3``."""
-    out = {}
-    for name, shape in raft_param_shapes().items():
-        src = name.replace(".downsample.1.", ".norm3.")
-        rng = np.random.default_rng([int(seed), zlib.crc32(src.encode())])
+    def rule(name, shape, rng):
         leaf = name.rsplit(".", 1)[1]
-        if leaf == "num_batches_tracked":
-            out[name] = torch.zeros((), dtype=torch.int64)
-            continue
         if len(shape) == 4:
-            v = rng.standard_normal(shape) * math.sqrt(2.0 / (shape[1] * shape[2] * shape[3]))
-        elif leaf == "running_var" or (leaf == "weight" and len(shape) == 1):
-            v = rng.uniform(0.5, 1.5, shape)
-        elif leaf in ("running_mean",) or ".norm" in name or ".downsample.1." in name:
-            v = 0.1 * rng.standard_normal(shape)
-        else:
-            v = 0.05 * rng.standard_normal(shape)
-        out[name] = torch.from_numpy(v.astype(np.float32))
-    return out
+            return he_normal(rng, shape)
+        if leaf == "running_var" or (leaf == "weight" and len(shape) == 1):
+            return rng.uniform(0.5, 1.5, shape)
+        if leaf in ("running_mean",) or ".norm" in name or ".downsample.1." in name:
+            return 0.1 * rng.standard_normal(shape)
+        return 0.05 * rng.standard_normal(shape)
+
+    shapes = raft_param_shapes()
+    drawn = random_tensors({n: s for n, s in shapes.items() if not n.endswith(".num_batches_tracked")}, seed,
+                           lambda name: name.replace(".downsample.1.", ".norm3."), rule)
+    return {n: drawn[n] if n in drawn else torch.zeros((), dtype=torch.int64) for n in shapes}
 
 
 def fold_batch_norm(weight, bias, running_mean, running_var, eps: float = BN_EPS):
     """Eval-mode BatchNorm as y = scale * x + shift, computed in fp64 -> (scale, shift) float32."""
-    scale = weight.double() / torch.sqrt(running_var.double() + eps)
-    shift = bias.double() - running_mean.double() * scale
-    return scale.float(), shift.float()
-
-
-def pack_conv_weight(w: torch.Tensor) -> torch.Tensor:
-    """[Cout,Cin,kh,kw] -> the kernel's [kh,kw,Cin,Cout] float32."""
-    return w.float().permute(2, 3, 1, 0).contiguous()
+    return tuple(t.float() for t in bn_affine(weight, bias, running_mean, running_var, eps))
 
 
 @dataclass
@@ -121,41 +110,24 @@ class ConvLayer:
     scale: torch.Tensor | None = None
     shift: torch.Tensor | None = None
 
-    def to(self, device):
-        mv = lambda t: None if t is None else t.to(device)
-        return ConvLayer(mv(self.w), mv(self.b), mv(self.scale), mv(self.shift))
-
 
 @dataclass
-class RaftWeights:
-    convs: dict = field(default_factory=dict)
-    device: torch.device = torch.device("cpu")
-    _moved: dict = field(default_factory=dict, repr=False)
+class RaftWeights(Weights):
+    convs: dict = field(default_factory=dict)       # name -> ConvLayer
 
     @classmethod
     def load(cls, path: str, small: bool = False) -> "RaftWeights":
         """A ``raft-things.pth``-style checkpoint: a state dict, possibly with the ``module.`` prefix of DataParallel."""
         if small:
             raise NotImplementedError("the small RAFT model is not built: dove_amd.flow runs the basic model only")
-        sd = torch.load(path, map_location="cpu", weights_only=True)
-        if isinstance(sd, dict) and isinstance(sd.get("state_dict"), dict):
-            sd = sd["state_dict"]
-        return cls.from_state_dict(sd)
+        return cls.from_state_dict(load_state_dict(path))
 
     @classmethod
     def from_state_dict(cls, sd: dict) -> "RaftWeights":
-        sd = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in sd.items()}
-        want = raft_param_shapes()
+        sd = strip(sd)
         if any(k.startswith("update_block.gru.convz.") or k.startswith("fnet.layer1.0.conv3.") for k in sd):
             raise NotImplementedError("this is a small-model RAFT checkpoint: dove_amd.flow runs the basic model only")
-        for name, shape in want.items():
-            if name not in sd:
-                raise ValueError(f"RAFT checkpoint: {name} is missing")
-            if tuple(sd[name].shape) != tuple(shape):
-                raise ValueError(f"RAFT checkpoint: {name} has shape {tuple(sd[name].shape)}, expected {tuple(shape)}")
-        for name in sd:
-            if name not in want:
-                raise ValueError(f"RAFT checkpoint: unexpected entry {name}")
+        checked(sd, raft_param_shapes(), "RAFT checkpoint", exact=True, say_shape=False)
         convs = {}
 
         def layer(name, norm=None):
@@ -186,16 +158,7 @@ class RaftWeights:
             w = torch.cat([sd[f"{u}.gru.convz{d}.weight"], sd[f"{u}.gru.convr{d}.weight"]], 0)
             b = torch.cat([sd[f"{u}.gru.convz{d}.bias"], sd[f"{u}.gru.convr{d}.bias"]], 0)
             convs[f"gru.convzr{d}"] = ConvLayer(pack_conv_weight(w), b.float().contiguous())
-        return cls(convs)
-
-    def to(self, device) -> "RaftWeights":
-        device = torch.device(device)
-        if device == self.device:
-            return self
-        key = str(device)
-        if key not in self._moved:
-            self._moved[key] = RaftWeights({k: v.to(device) for k, v in self.convs.items()}, device)
-        return self._moved[key]
+        return cls(convs=convs)
 
 
 # ------------------------------------------------------------------ planning ------------------------------------------------------------------

@@ -1,11 +1,15 @@
 """What every image-quality metric shares, written once: image intake, the walk over groups of frames, the search for files in a
-``--metric_weights`` directory, the state-dict loader, the pyiqa-style metric object and the ``score`` command-line loop.
+``--metric_weights`` directory, the state-dict loader, the pyiqa-style metric object, the ``score`` command-line loop and the per-clip
+evaluation loop of the video metrics' commands.
 
-This module imports none of the metric modules (metrics, percep, niqe, clipiqa, musiq); they import it.  A metric module keeps what is
-its own: the network walk, its ``group_size`` formula, its ``COUNTERS`` and its weights class.  ``metrics.REGISTRY`` declares the metrics."""
+This module imports none of the metric modules (metrics, percep, niqe, clipiqa, musiq, flow, fastvqa); they import it.  A metric module
+keeps what is its own: the network walk, its ``group_size`` formula, its ``COUNTERS``, the shapes and the packing of its checkpoint.  What
+the weights classes share is in ``netweights``.  ``metrics.REGISTRY`` declares the metrics."""
 from __future__ import annotations
 
 import glob
+import json
+import math
 import os
 
 import numpy as np
@@ -142,3 +146,47 @@ def score_folder(args, load_weights, score_fn) -> dict:
     if scores:
         print(f"average: {float(np.mean(list(scores.values()))):.4f}")
     return scores
+
+
+def list_clips(pred_root: str) -> dict:
+    """{os.path.splitext stem: path} of the folders, ``.npy`` and ``.y4m`` entries of ``pred_root``."""
+    clips = {}
+    for item in sorted(os.listdir(pred_root)):
+        path = os.path.join(pred_root, item)
+        if os.path.isdir(path) or item.lower().endswith((".npy", ".y4m")):
+            clips[os.path.splitext(item)[0]] = path
+    return clips
+
+
+def summarize(results: dict, keys) -> dict:
+    """per_sample, per key the average of the (rounded) per-sample values that are numbers, count."""
+    average = {}
+    for key in keys:
+        vals = [v[key] for v in results.values() if not math.isnan(v[key])]
+        if results:
+            average[key] = round(sum(vals) / len(vals), 4) if vals else float("nan")
+    return {"per_sample": results, "average": average, "count": len(results)}
+
+
+def process_clips(pred_root: str, out_path: str, out_name: str, keys, clip_fn) -> dict:
+    """The loop of a per-clip evaluation command: every clip of ``pred_root`` is read by ``prepost.load_frames``; ``clip_fn(name, frames)``
+    gives its rounded {key: value} (``None``: the clip is left out; an exception is reported and the clip left out); the summary is
+    printed and written to ``out_path/out_name``."""
+    from . import prepost
+    results = {}
+    for name, path in list_clips(pred_root).items():
+        try:
+            r = clip_fn(name, prepost.load_frames(path))
+            if r is not None:
+                results[name] = r
+        except Exception as e:
+            print(f"Error processing {name}: {e}")
+    output = summarize(results, keys)
+    print(f"\nProcessed {output['count']} samples.")
+    print(f"Average score: {output['average']}")
+    os.makedirs(out_path, exist_ok=True)
+    path = os.path.join(out_path, out_name)
+    with open(path, "w") as f:
+        json.dump(output, f, indent=2)
+    print(f"Results saved to: {path}")
+    return output

@@ -29,16 +29,15 @@ from __future__ import annotations
 
 import argparse
 import math
-import zlib
 from dataclasses import dataclass, field
 
 import numpy as np
 import torch
 
 from . import iqa, ops
-from .flow import pack_conv_weight
 from .iqa import ACTIVATION_BUDGET, GpuMetric, find_file, for_groups, load_state_dict, score_folder
-from .percep import _checked, _strip, _Weights
+from .netweights import (Weights, checked, device_tables, fan_in_normal, nearest_index, pack_conv_weight, pack_linear_weight, prenorm_mlp_f32,
+                         random_tensors, strip)
 
 PATCH, HASH_GRID = 32, 10
 SCALE_SIDES = (224, 384)                            # the longer sides of the two resized scales; the third scale is the original
@@ -69,10 +68,8 @@ def scale_sizes(H: int, W: int):
 
 
 def hash_index(count: int, grid: int = HASH_GRID) -> np.ndarray:
-    """torch's nearest-neighbour ``F.interpolate`` of arange(grid) to ``count`` points: floor(i * (grid / count)) in float32, at most
-    grid - 1 (pyiqa's get_hashed_spatial_pos_emb_index)."""
-    scale = np.float32(grid) / np.float32(count)
-    return np.minimum(np.floor(np.arange(count, dtype=np.float32) * scale).astype(np.int64), grid - 1)
+    """``nearest_index`` on the position grid (pyiqa's get_hashed_spatial_pos_emb_index)."""
+    return nearest_index(count, grid)
 
 
 _GEOMETRY = {}
@@ -93,12 +90,6 @@ def token_geometry(H: int, W: int) -> dict:
         tokens = torch.tensor(rows, dtype=torch.int32).reshape(-1, 4)
         _GEOMETRY[key] = {"scales": scales, "counts": counts, "tokens": tokens, "length": len(rows) + 1, "device": {}}
     return _GEOMETRY[key]
-
-
-def _device_tokens(geo: dict, device) -> torch.Tensor:
-    if device not in geo["device"]:
-        geo["device"][device] = geo["tokens"].to(device)
-    return geo["device"][device]
 
 
 def group_size(h: int, w: int, budget: int | None = None) -> int:
@@ -148,19 +139,14 @@ def random_musiq_state(seed: int, num_classes: int = 1) -> dict:
     std 0.5, so that tokens differ by where they sit as much as by what they show.  Each tensor has its own generator keyed by (seed, name,
     WEIGHT_DRAW); tests/test_musiq_cpu.py asserts, under the fp64 restatement, that with this draw the scores of the tests' images
     separate their noise levels and that the attention's softmax is neither uniform nor one-hot."""
-    sd = {}
-    for name, shape in param_shapes(num_classes).items():
-        rng = np.random.default_rng([int(seed), zlib.crc32(f"musiq.{name}".encode()), WEIGHT_DRAW])
+    def rule(name, shape, rng):
         if name.endswith(("position_emb", "scale_emb", "cls")):
-            v = 0.5 * rng.standard_normal(shape)
-        elif len(shape) >= 2:
-            v = rng.standard_normal(shape) / math.sqrt(float(np.prod(shape[1:])))
-        elif name.endswith(".weight"):
-            v = rng.uniform(0.5, 1.5, shape)
-        else:
-            v = 0.05 * rng.standard_normal(shape)
-        sd[name] = torch.from_numpy(np.asarray(v, dtype=np.float32))
-    return sd
+            return 0.5 * rng.standard_normal(shape)
+        if len(shape) >= 2:
+            return fan_in_normal(rng, shape)
+        return rng.uniform(0.5, 1.5, shape) if name.endswith(".weight") else 0.05 * rng.standard_normal(shape)
+
+    return random_tensors(param_shapes(num_classes), seed, lambda name: f"musiq.{name}", rule, (WEIGHT_DRAW,))
 
 
 def standardise(w: torch.Tensor) -> torch.Tensor:
@@ -172,18 +158,19 @@ def standardise(w: torch.Tensor) -> torch.Tensor:
 
 
 @dataclass
-class MusiqWeights(_Weights):
+class MusiqWeights(Weights):
     """``convs``: the standardised stem convs (weight [k,k,cin,cout], no bias); ``params``: every other tensor by a short name."""
+    convs: dict = field(default_factory=dict)
     params: dict = field(default_factory=dict)
     num_classes: int = 1
 
     @classmethod
     def from_state_dict(cls, sd: dict) -> "MusiqWeights":
-        sd = _strip(sd["params"] if isinstance(sd.get("params"), dict) else sd)
+        sd = strip(sd["params"] if isinstance(sd.get("params"), dict) else sd)
         k = int(sd["head.weight"].shape[0]) if "head.weight" in sd and sd["head.weight"].dim() == 2 else 1
-        sd = _checked(sd, param_shapes(k), "MUSIQ checkpoint")
+        sd = checked(sd, param_shapes(k), "MUSIQ checkpoint")
         f32 = lambda t: t.detach().float().contiguous()
-        lin = lambda w: f32(w.detach().float().t())[None, None]                  # [out,in] -> the 1 x 1 walk's [1,1,in,out]
+        lin = pack_linear_weight                    # [out,in] -> the 1 x 1 walk's [1,1,in,out]
         convs = {name: (pack_conv_weight(standardise(sd[f"{name}.weight"])), torch.zeros(0)) for name, _, _, _ in STEM_CONVS}   # one rounding
         p = {}
         for name, _ in STEM_NORMS:
@@ -210,18 +197,12 @@ class MusiqWeights(_Weights):
         """From a ``--metric_weights`` directory: the first ``musiq*.pth`` (pyiqa's checkpoint; a top-level ``params`` is unwrapped)."""
         return cls.from_state_dict(load_state_dict(find_file(directory, FILE_PATTERN)))
 
-    def to(self, device):
-        new = super().to(device)
-        if new is not self and new.params is self.params:
-            new.params = {n: t.to(new.device) for n, t in self.params.items()}
-        return new
-
 
 # -------------------------------------------------------------------- walk --------------------------------------------------------------------
 def patches(images: torch.Tensor, before: int = 0, side: int = PATCH):
     """Every token's 2 v - 1 patch of a group of images on the device -> (float32 [g T,side,side,3], geometry)."""
     geo = token_geometry(images.shape[2], images.shape[3])
-    return ops.musiq_patches_f32(images, geo["scales"], _device_tokens(geo, images.device), before, side), geo
+    return ops.musiq_patches_f32(images, geo["scales"], device_tables(geo, images.device, ("tokens",))[0], before, side), geo
 
 
 def _gn(W: MusiqWeights, name: str, x, eps, **kw):
@@ -255,11 +236,8 @@ def encoder(W: MusiqWeights, x: torch.Tensor) -> torch.Tensor:
         a = ops.mha_f32(qkv[..., :DIM], qkv[..., DIM:2 * DIM], qkv[..., 2 * DIM:], 1.0 / math.sqrt(DIM // HEADS))
         del qkv
         ops.linear_f32(a.view(g * T, DIM), p[f"{i}.out.weight"], p[f"{i}.out.bias"], residual=rows, out=rows)
-        h = ops.layernorm_f32(rows, p[f"{i}.norm2.weight"], p[f"{i}.norm2.bias"], LN_EPS, out=h)
-        m = ops.linear_f32(h, p[f"{i}.fc1.weight"], p[f"{i}.fc1.bias"])
-        ops.gelu_f32(m, out=m)
-        ops.linear_f32(m, p[f"{i}.fc2.weight"], p[f"{i}.fc2.bias"], residual=rows, out=rows)
-        del h, a, m
+        prenorm_mlp_f32(rows, h, p, f"{i}.norm2", f"{i}.fc1", f"{i}.fc2", LN_EPS)
+        del h, a
     return x
 
 
@@ -271,7 +249,7 @@ def features(W: MusiqWeights, images: torch.Tensor) -> torch.Tensor:
     p = W.params
     emb = ops.linear_f32(y.view(y.shape[0], EMBED_IN), p["embedding.weight"], p["embedding.bias"])
     del y
-    x = encoder(W, ops.musiq_embed_f32(emb, p["pos"], p["scale"], p["cls"], _device_tokens(geo, images.device)))
+    x = encoder(W, ops.musiq_embed_f32(emb, p["pos"], p["scale"], p["cls"], device_tables(geo, images.device, ("tokens",))[0]))
     return ops.layernorm_f32(x[:, 0], p["encoder_norm.weight"], p["encoder_norm.bias"], LN_EPS)
 
 

@@ -18,7 +18,6 @@ sized so that the live activations of a group stay under ``ACTIVATION_BUDGET``; 
 """
 from __future__ import annotations
 
-import math
 import zlib
 from dataclasses import dataclass, field
 
@@ -26,8 +25,8 @@ import numpy as np
 import torch
 
 from . import iqa, ops
-from .flow import pack_conv_weight
 from .iqa import ACTIVATION_BUDGET, FLOAT32_DTYPES, GpuMetric, as_nchw, find_file, for_groups, load_state_dict
+from .netweights import Weights, checked, he_normal, pack_conv_weight, random_tensors, strip
 
 ALEX_CONVS = ((0, 64, 3, 11, 4, 2), (3, 192, 64, 5, 1, 2), (6, 384, 192, 3, 1, 1), (8, 256, 384, 3, 1, 1), (10, 256, 256, 3, 1, 1))
 VGG_STAGES = (((0, 64, 3), (2, 64, 64)), ((5, 128, 64), (7, 128, 128)), ((10, 256, 128), (12, 256, 256), (14, 256, 256)),
@@ -60,90 +59,43 @@ def backbone_param_shapes(net: str) -> dict:
 
 
 def _random_backbone(seed: int, net: str) -> dict:
-    out = {}
-    for name, shape in backbone_param_shapes(net).items():
-        rng = np.random.default_rng([int(seed), zlib.crc32(f"{net}.{name}".encode())])
-        v = rng.standard_normal(shape) * math.sqrt(2.0 / (shape[1] * shape[2] * shape[3])) if len(shape) == 4 else \
-            0.05 * rng.standard_normal(shape)
-        out[name] = torch.from_numpy(v.astype(np.float32))
-    return out
+    rule = lambda name, shape, rng: he_normal(rng, shape) if len(shape) == 4 else 0.05 * rng.standard_normal(shape)
+    return random_tensors(backbone_param_shapes(net), seed, lambda name: f"{net}.{name}", rule)
+
+
+def _uniform(seed: int, key: str, channels: int) -> torch.Tensor:
+    rng = np.random.default_rng([int(seed), zlib.crc32(key.encode())])
+    return torch.from_numpy(rng.uniform(0.05, 1.0, (1, channels, 1, 1)).astype(np.float32))
 
 
 def random_lpips_state(seed: int, net: str):
     """Rule-generated (backbone_sd, lin_sd) for tests and tools: conv weights normal with He std, biases 0.05 * normal, lin uniform in
     [0.05, 1]."""
-    lin = {}
-    for k, c in enumerate(LPIPS_CHANNELS[net]):
-        rng = np.random.default_rng([int(seed), zlib.crc32(f"{net}.lin{k}".encode())])
-        lin[f"lin{k}.model.1.weight"] = torch.from_numpy(rng.uniform(0.05, 1.0, (1, c, 1, 1)).astype(np.float32))
-    return _random_backbone(seed, net), lin
+    return _random_backbone(seed, net), {f"lin{k}.model.1.weight": _uniform(seed, f"{net}.lin{k}", c) for k, c in enumerate(LPIPS_CHANNELS[net])}
 
 
 def random_dists_state(seed: int):
     """Rule-generated (backbone_sd, ab_sd): the VGG16 of ``random_lpips_state`` and alpha, beta uniform in [0.05, 1]."""
-    ab = {}
-    for name in ("alpha", "beta"):
-        rng = np.random.default_rng([int(seed), zlib.crc32(f"dists.{name}".encode())])
-        ab[name] = torch.from_numpy(rng.uniform(0.05, 1.0, (1, sum(DISTS_CHANNELS), 1, 1)).astype(np.float32))
-    return _random_backbone(seed, "vgg"), ab
-
-
-def _strip(sd: dict) -> dict:
-    if isinstance(sd, dict) and isinstance(sd.get("state_dict"), dict):
-        sd = sd["state_dict"]
-    return {(k[len("module."):] if k.startswith("module.") else k): v for k, v in sd.items()}
-
-
-def _checked(sd: dict, want: dict, what: str) -> dict:
-    for name, shape in want.items():
-        if name not in sd:
-            raise ValueError(f"{what}: {name} is missing (expected shape {tuple(shape)})")
-        if tuple(sd[name].shape) != tuple(shape):
-            raise ValueError(f"{what}: {name} has shape {tuple(sd[name].shape)}, expected {tuple(shape)}")
-    return sd
+    return _random_backbone(seed, "vgg"), {name: _uniform(seed, f"dists.{name}", sum(DISTS_CHANNELS)) for name in ("alpha", "beta")}
 
 
 def _pack_backbone(sd: dict, net: str) -> dict:
-    sd = _checked(_strip(sd), backbone_param_shapes(net), f"{'AlexNet' if net == 'alex' else 'VGG16'} checkpoint")
+    sd = checked(strip(sd), backbone_param_shapes(net), f"{'AlexNet' if net == 'alex' else 'VGG16'} checkpoint")
     nums = [c[0] for c in ALEX_CONVS] if net == "alex" else [c[0] for stage in VGG_STAGES for c in stage]
     return {n: (pack_conv_weight(sd[f"features.{n}.weight"]), sd[f"features.{n}.bias"].float().contiguous()) for n in nums}
 
 
 @dataclass
-class _Weights:
+class LpipsWeights(Weights):
     convs: dict = field(default_factory=dict)       # features.N -> (w [kh,kw,cin,cout], bias)
-    device: torch.device = torch.device("cpu")
-    _copies: dict = field(default_factory=dict, repr=False)      # device -> the copy made for it, so a metric uploads once
-
-    _TENSOR_LISTS = ()
-
-    def to(self, device):
-        device = torch.device(device)
-        if device.type == "cuda" and device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        if device == self.device:
-            return self
-        if device not in self._copies:
-            new = type(self)(**{k: getattr(self, k) for k in self.__dataclass_fields__ if k != "_copies"})
-            new.convs = {n: (w.to(device), b.to(device)) for n, (w, b) in self.convs.items()}
-            for name in self._TENSOR_LISTS:
-                setattr(new, name, [t.to(device) for t in getattr(self, name)])
-            new.device = device
-            self._copies[device] = new
-        return self._copies[device]
-
-
-@dataclass
-class LpipsWeights(_Weights):
     net: str = "alex"
     lins: list = field(default_factory=list)        # five float32 [C]
-    _TENSOR_LISTS = ("lins",)
 
     @classmethod
     def from_state_dicts(cls, backbone_sd: dict, lin_sd: dict, net: str) -> "LpipsWeights":
         convs = _pack_backbone(backbone_sd, net)
         want = {f"lin{k}.model.1.weight": (1, c, 1, 1) for k, c in enumerate(LPIPS_CHANNELS[net])}
-        lin_sd = _checked(_strip(lin_sd), want, f"LPIPS v0.1 ({net}) linear layers")
+        lin_sd = checked(strip(lin_sd), want, f"LPIPS v0.1 ({net}) linear layers")
         return cls(convs=convs, net=net, lins=[lin_sd[name].float().reshape(-1).contiguous() for name in want])
 
     @classmethod
@@ -152,16 +104,16 @@ class LpipsWeights(_Weights):
 
 
 @dataclass
-class DistsWeights(_Weights):
+class DistsWeights(Weights):
+    convs: dict = field(default_factory=dict)       # as LpipsWeights.convs
     alpha: list = field(default_factory=list)       # six float64 [C], divided by sum(alpha) + sum(beta)
     beta: list = field(default_factory=list)
-    _TENSOR_LISTS = ("alpha", "beta")
 
     @classmethod
     def from_state_dicts(cls, backbone_sd: dict, ab_sd: dict) -> "DistsWeights":
         convs = _pack_backbone(backbone_sd, "vgg")
         total = sum(DISTS_CHANNELS)
-        ab_sd = _checked(_strip(ab_sd), {"alpha": (1, total, 1, 1), "beta": (1, total, 1, 1)}, "DISTS weights")
+        ab_sd = checked(strip(ab_sd), {"alpha": (1, total, 1, 1), "beta": (1, total, 1, 1)}, "DISTS weights")
         a, b = ab_sd["alpha"].double().reshape(-1), ab_sd["beta"].double().reshape(-1)
         w_sum = a.sum() + b.sum()
         split = lambda t: [s.contiguous() for s in torch.split(t / w_sum, list(DISTS_CHANNELS))]

@@ -95,3 +95,22 @@ def test_metric_object_and_group_walk(name, monkeypatch):
             before = counters["groups"]
             assert torch.equal(DIRECT[name](W, pred.to(DEV), ref.to(DEV), group=group), got), group
             assert counters["groups"] == before + walked
+
+
+def test_weights_to_names_the_current_device_and_frees_with_its_owner():
+    """dove_amd.netweights.Weights.to on the hand-made container of tests/test_netweights_cpu.py: ``cuda`` is the current index, one
+    copy per device, every leaf there, and the copy's memory goes when the container goes."""
+    import test_netweights_cpu as TN
+    torch.cuda.synchronize()
+    live = torch.cuda.memory_allocated()
+    c = TN.container(256)
+    here = torch.device("cuda", torch.cuda.current_device())
+    moved = c.to("cuda")
+    assert moved is c.to(here) and moved is c.to(f"cuda:{here.index}") and moved.to("cuda") is moved and len(c._copies) == 1
+    TN.check_copy(c, moved, here)
+    for k, t in TN.tensor_leaves(moved).items():
+        assert torch.equal(t.cpu(), TN.tensor_leaves(c)[k]), k
+    assert torch.cuda.memory_allocated() > live
+    del moved, t, c
+    gc.collect()
+    assert torch.cuda.memory_allocated() == live
