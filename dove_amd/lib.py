@@ -278,6 +278,10 @@ SIGNATURES = {
     "dove_swin3d_patch_merge_f32": [_VP, _LL, _I, _I, _I, _VP, _VP],
     "dove_swin3d_window_attention_f32": [_VP, _VP, _VP, _LL, _LL, _I, _I, _F, _VP, _VP, _I, _VP, _VP, _VP, _I, _VP, _LL, _VP],
     "dove_vqa_head_f64": [_VP, _LL, _I, _I, _I, _VP, _VP, _I, _VP, _VP, _VP, _VP],
+    # DOVER's aesthetic branch (csrc/convnext3d.hip): the depthwise 3 x 7 x 7 conv and the resized view
+    "dove_dwconv3d_f32": [_VP, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP],
+    "dove_vqa_resized_view_f32": [C.POINTER(ImageView), _I, _I, _I, _VP, _I, _VP, _VP, _I, _VP, _VP, _I, _I, _I, C.POINTER(C.c_double),
+                                  C.POINTER(C.c_double), _I, _VP, _VP],
     # PNG encoder (csrc/png.hip): whole files on the device, and its deflate stage on a plain buffer
     "dove_png_encode": [C.POINTER(ImageView), _I, _I, _I, _I, _VP, C.c_size_t, _VP, _VP, _VP],
     "dove_zlib_huffman": [_VP, _LL, _LL, _VP, C.c_size_t, _VP, _VP, _VP],
@@ -316,6 +320,7 @@ PLAIN = {"dove_last_error": (C.c_char_p, []), "dove_abi_version": (C.c_int, []),
          "dove_clip_attnpool_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
          "dove_mha_f32_tiles": (None, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
          "dove_swin3d_attention_tiles": (None, [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+         "dove_dwconv3d_tile": (None, [_I, _I, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
          "dove_png_segment_rows": (C.c_int, [_I, _I]),
          "dove_png_bound": (C.c_size_t, [_I, _I, _I]),
          "dove_png_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I]),

@@ -6,6 +6,7 @@ import ctypes as C
 import math
 from dataclasses import dataclass
 
+import numpy as np
 import torch
 
 from . import lib as L
@@ -1748,4 +1749,109 @@ def vqa_head_f64(features: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2:
     out = torch.empty(n, dtype=torch.float64, device=features.device)
     L.check(L.load().dove_vqa_head_f64(L.ptr(features), D, n, T, D, L.ptr(w1), L.ptr(b1), hid, L.ptr(w2), L.ptr(b2), L.ptr(out), L.stream_ptr()),
             "dove_vqa_head_f64")
+    return out
+
+
+# ---- DOVER's aesthetic branch (csrc/convnext3d.hip): the depthwise 3 x 7 x 7 conv and the resized view ------------------------------------
+def dwconv3d_tile(h: int, w: int) -> tuple:
+    """(rows, columns) of the output tile one workgroup of ``dwconv3d_f32`` owns on an h x w map; needs no device."""
+    th, tw = C.c_int(0), C.c_int(0)
+    L.load().dove_dwconv3d_tile(int(h), int(w), C.byref(th), C.byref(tw))
+    return th.value, tw.value
+
+
+def dwconv3d_f32(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Depthwise Conv3d, kernel (3,7,7), zero padding (1,3,3), stride 1, on a channels-last map float32 [B,D,H,W,C]; ``w`` float32
+    [3,7,7,C] (tap-major), ``bias`` [C].  Exact fp32: one fmaf chain per output from the bias over the taps in (kd, kh, kw) order.
+    ``out`` must not alias ``x``."""
+    B, D, H, W, Cc = _token_map(x, "dwconv3d_f32")
+    L.require_cuda(w, bias)
+    if not x.is_contiguous():
+        raise ValueError("dwconv3d_f32: x must be contiguous")
+    if w.dtype != torch.float32 or tuple(w.shape) != (3, 7, 7, Cc) or not w.is_contiguous() or bias.dtype != torch.float32 or \
+            tuple(bias.shape) != (Cc,) or not bias.is_contiguous():
+        raise ValueError(f"dwconv3d_f32: need contiguous float32 w [3,7,7,{Cc}] and bias [{Cc}], got {tuple(w.shape)} and {tuple(bias.shape)}")
+    if out is None:
+        out = torch.empty_like(x)
+    elif out.shape != x.shape or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("dwconv3d_f32: out must be contiguous float32 of x's shape")
+    elif out.data_ptr() < x.data_ptr() + 4 * x.numel() and x.data_ptr() < out.data_ptr() + 4 * out.numel():
+        raise ValueError("dwconv3d_f32: out must not alias x (every output reads 147 inputs around it)")
+    L.check(L.load().dove_dwconv3d_f32(L.ptr(x), B, D, H, W, Cc, L.ptr(w), L.ptr(bias), L.ptr(out), L.stream_ptr()), "dove_dwconv3d_f32")
+    return out
+
+
+_RESIZE_TAPS = {}
+
+
+def resize_taps(n_in: int, n_out: int, antialias: bool = True) -> dict:
+    """The tap table of one axis of torch's bilinear ``F.interpolate(align_corners=False)`` from ``n_in`` to ``n_out`` samples, in fp64:
+    ``first`` int32 [n_out], ``count`` int32 [n_out], ``weights`` float64 [n_out,max] (zero past the count).  ``antialias``: the triangle
+    filter of support max(in / out, 1); else two taps at max(0, scale (i + 0.5) - 0.5), the upper index clamped.  Taps of weight 0 at
+    either end are dropped (n_in == n_out is the identity table).  Cached per (n_in, n_out, mode); ``device``: the uploads, per device."""
+    key = (int(n_in), int(n_out), bool(antialias))
+    if key in _RESIZE_TAPS:
+        return _RESIZE_TAPS[key]
+    if n_in < 1 or n_out < 1:
+        raise ValueError(f"resize_taps: {n_in} -> {n_out} samples")
+    scale = n_in / n_out
+    rows = []
+    for i in range(n_out):
+        if antialias:
+            support, c = max(scale, 1.0), scale * (i + 0.5)
+            lo, hi = max(0, int(c - support + 0.5)), min(n_in, int(c + support + 0.5))
+            wts = [max(0.0, 1.0 - abs((j - c + 0.5) / support)) for j in range(lo, hi)]
+            total = sum(wts)
+            wts = [v / total for v in wts]
+        else:
+            src = max(0.0, scale * (i + 0.5) - 0.5)
+            lo = min(int(src), n_in - 1)
+            lam = src - lo
+            wts = [1.0 - lam, lam] if lo + 1 < n_in else [1.0]       # the clamped upper index is the lower one: (1 - l) v + l v
+        while len(wts) > 1 and wts[-1] == 0.0:
+            wts.pop()
+        while len(wts) > 1 and wts[0] == 0.0:
+            wts.pop(0)
+            lo += 1
+        rows.append((lo, wts))
+    most = max(len(wts) for _, wts in rows)
+    tab = np.zeros((n_out, 2), dtype=np.int32)
+    weights = np.zeros((n_out, most), dtype=np.float64)
+    for i, (lo, wts) in enumerate(rows):
+        tab[i] = (lo, len(wts))
+        weights[i, :len(wts)] = wts
+    assert tab[:, 0].min() >= 0 and (tab[:, 0] + tab[:, 1]).max() <= n_in
+    taps = {"first": tab[:, 0].copy(), "count": tab[:, 1].copy(), "table": tab, "weights": weights, "max": most, "device": {}}
+    _RESIZE_TAPS[key] = taps
+    return taps
+
+
+def _taps_on(taps: dict, device):
+    if device not in taps["device"]:
+        taps["device"][device] = (torch.from_numpy(taps["table"]).to(device), torch.from_numpy(taps["weights"]).to(device))
+    return taps["device"][device]
+
+
+def vqa_resized_view_f32(clip: torch.Tensor, frames: torch.Tensor, size, mean, std, antialias: bool = True, cols: bool = False) -> torch.Tensor:
+    """clip: an [F,3,H,W] view (uint8, or float32 / bfloat16 in [0,1]; any strides, no copy), ``frames`` int32 [T] on the device, ``size``
+    = (oh, ow) -> float32 [T,oh,ow,3]: every picked frame resized bilinearly (``resize_taps``, both axes) in fp64 on X (the uint8 value
+    or 255 v), then (X - mean) / std, rounded once.  ``cols``: the same values as the (2,4,4) patch embedding's GEMM rows, float32
+    [T/2,oh/4,ow/4,96], in ``vqa_fragments_f32``'s column order (csrc/convnext3d.hip)."""
+    if clip.dim() != 4 or clip.shape[1] != 3 or not clip.is_cuda:
+        raise ValueError(f"vqa_resized_view_f32: need an [F,3,H,W] view on the HIP device, got {tuple(clip.shape)} on {clip.device}")
+    _strided_on_device("vqa_resized_view_f32", clip)
+    L.require_cuda(frames)
+    if frames.dtype != torch.int32 or frames.dim() != 1 or frames.shape[0] == 0:
+        raise ValueError("vqa_resized_view_f32: frames must be int32 [T], T >= 1")
+    T, (oh, ow) = frames.shape[0], (int(size[0]), int(size[1]))
+    if oh < 1 or ow < 1 or (cols and (T % 2 or oh % 4 or ow % 4)):
+        raise ValueError(f"vqa_resized_view_f32: the patch rows need an even T and view sides that are multiples of 4, got {T} x {oh} x {ow}")
+    ty, tx = resize_taps(clip.shape[2], oh, antialias), resize_taps(clip.shape[3], ow, antialias)
+    (ytab, yw), (xtab, xw) = _taps_on(ty, clip.device), _taps_on(tx, clip.device)
+    out = torch.empty((T // 2, oh // 4, ow // 4, 96) if cols else (T, oh, ow, 3), dtype=torch.float32, device=clip.device)
+    v = _image_view(clip)
+    L.check(L.load().dove_vqa_resized_view_f32(C.byref(v), clip.shape[0], clip.shape[2], clip.shape[3], L.ptr(frames), T, L.ptr(ytab), L.ptr(yw),
+                                               ty["max"], L.ptr(xtab), L.ptr(xw), tx["max"], oh, ow, (C.c_double * 3)(*map(float, mean)),
+                                               (C.c_double * 3)(*map(float, std)), int(bool(cols)), L.ptr(out), L.stream_ptr()),
+            "dove_vqa_resized_view_f32")
     return out

@@ -969,6 +969,24 @@ int dove_swin3d_window_attention_f32(const float* q, const float* k, const float
 int dove_vqa_head_f64(const float* features, long long ld, int clips, int tokens, int dim, const float* w1, const float* b1, int hidden,
                       const float* w2, const float* b2, double* out, void* stream);
 
+/* DOVER's aesthetic branch (csrc/convnext3d.hip; tests/dover_ref.py is the definition): what an inflated ConvNeXt-Tiny needs
+ * beside the operators above.  Maps are channels-last fp32 [b][d][h][w][c], dense; no atomics, identical bits on repetition, a sample's result
+ * independent of the batch.  Neither needs a workspace.
+ *   dwconv3d_f32: depthwise Conv3d, kernel (3,7,7), zero padding (1,3,3), stride 1.  weight is [3][7][7][c] (tap-major), bias [c]; c a multiple
+ *     of 4; out must not overlap x; 16-byte aligned pointers.  Exact fp32: out = one fmaf chain from the bias over the taps in (kd, kh, kw)
+ *     order, each ascending, tap (kd, kh, kw) reading x at (d + kd - 1, h + kh - 3, w + kw - 3); taps outside the map are skipped or multiply
+ *     a 0.  dove_dwconv3d_tile reports the th x tw output tile of a workgroup on an h x w map (tw is 7 or 8, th at most 16).
+ *   vqa_resized_view_f32: clip as in vqa_fragments_f32.  Output pixel (t, y, x) of the [t][oh][ow] view is frame frames[t] (clamped into the
+ *     clip) resampled by two separable tap tables on the device: ytab [oh][2] int32 (first source row, tap count <= ymax) and yw [oh][ymax]
+ *     fp64 weights, xtab / xw likewise.  sum_j yw[j] (sum_i xw[i] X[first_y + j][first_x + i]) in fp64 with X the u8 value or 255.0 v, source
+ *     coordinates clamped into the frame, then (sum - mean_c) / std_c, rounded once.  cols as in vqa_fragments_f32: [t][oh][ow][3], or the
+ *     patch GEMM's rows [t / 2][oh / 4][ow / 4][96] (t even, oh and ow multiples of 4). */
+void dove_dwconv3d_tile(int h, int w, int* th, int* tw);
+int dove_dwconv3d_f32(const float* x, int b, int d, int h, int w, int c, const float* weight, const float* bias, float* out, void* stream);
+int dove_vqa_resized_view_f32(const dove_image_view* clip, int frames_in, int h, int w, const int* frames, int t, const int* ytab, const double* yw,
+                              int ymax, const int* xtab, const double* xw, int xmax, int oh, int ow, const double* mean, const double* std,
+                              int cols, float* out, void* stream);
+
 /* ---- PNG encoder (csrc/png.hip; tests/png_ref.py is the bit-exact definition of the filtered stream) ----
  * png_encode: img is a strided [n,channels,h,w] view as above (channels 3 = RGB, 1 = grey; u8 as it is, f32 / bf16 quantised as
  *   dove_postprocess_u8 does, trunc(clamp(255 x, 0, 255))).  Frame i becomes a complete 8-bit, non-interlaced PNG file at
