@@ -2,7 +2,7 @@
 ``--metric_weights`` directory, the state-dict loader, the pyiqa-style metric object, the ``score`` command-line loop and the per-clip
 evaluation loop of the video metrics' commands.
 
-This module imports none of the metric modules (metrics, percep, niqe, clipiqa, musiq, flow, fastvqa); they import it.  A metric module
+This module imports none of the metric modules (metrics, percep, niqe, clipiqa, musiq, flow, fastvqa, maniqa); they import it.  A metric module
 keeps what is its own: the network walk, its ``group_size`` formula, its ``COUNTERS``, the shapes and the packing of its checkpoint.  What
 the weights classes share is in ``netweights``.  ``metrics.REGISTRY`` declares the metrics."""
 from __future__ import annotations
@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 # Live fp32 activations of one group of frames, the same for every network metric: each module's ``group_size`` says how many frames that is
-# (percep: four 720p pairs through VGG16; clipiqa: 36 frames of 720 x 1280; musiq: 25).
+# (percep: four 720p pairs through VGG16; clipiqa: 36 frames of 720 x 1280; musiq: 25; maniqa: 2).
 ACTIVATION_BUDGET = 4 << 30
 IMAGE_EXTENSIONS = (".png", ".jpg", ".jpeg", ".bmp")
 FLOAT32_DTYPES = (torch.uint8, torch.float32)       # what the fp32 networks read in place; every other dtype is cast to float32

@@ -282,6 +282,15 @@ SIGNATURES = {
     "dove_dwconv3d_f32": [_VP, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP],
     "dove_vqa_resized_view_f32": [C.POINTER(ImageView), _I, _I, _I, _VP, _I, _VP, _VP, _I, _VP, _VP, _I, _I, _I, C.POINTER(C.c_double),
                                   C.POINTER(C.c_double), _I, _VP, _VP],
+    # MANIQA (csrc/maniqa.hip): the batched strided GEMM, row softmax, 2-D window attention, crop gather, cls / positions, scale-add-transpose
+    # and the fp64 weighted head
+    "dove_bmm_f32": [_VP, _LL, _LL, _VP, _LL, _LL, _VP, _VP, _LL, _LL, _VP, _LL, _LL, _I, _I, _I, _I, _F, _I, _VP],
+    "dove_softmax_rows_f32": [_VP, _LL, _LL, _I, _VP, _LL, _VP],
+    "dove_window_attention_f32": [_VP, _VP, _VP, _LL, _LL, _I, _I, _I, _F, _VP, _I, _VP, _VP, _I, _VP, _LL, _VP],
+    "dove_maniqa_crops_f32": [C.POINTER(ImageView), _I, _I, _I, _I, _VP, _I, _I, _I, _VP, _VP],
+    "dove_maniqa_tokens_f32": [_VP, _VP, _VP, _LL, _I, _I, _VP, _VP],
+    "dove_mix_f32": [_VP, _LL, _LL, _VP, _LL, _LL, _F, _I, _I, _I, _I, _VP, _LL, _LL, _VP],
+    "dove_maniqa_score": [_VP, _LL, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP],
     # PNG encoder (csrc/png.hip): whole files on the device, and its deflate stage on a plain buffer
     "dove_png_encode": [C.POINTER(ImageView), _I, _I, _I, _I, _VP, C.c_size_t, _VP, _VP, _VP],
     "dove_zlib_huffman": [_VP, _LL, _LL, _VP, C.c_size_t, _VP, _VP, _VP],
@@ -321,6 +330,9 @@ PLAIN = {"dove_last_error": (C.c_char_p, []), "dove_abi_version": (C.c_int, []),
          "dove_mha_f32_tiles": (None, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
          "dove_swin3d_attention_tiles": (None, [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
          "dove_dwconv3d_tile": (None, [_I, _I, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+         "dove_bmm_f32_tiles": (None, [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+         "dove_bmm_f32_kernel_name": (C.c_char_p, [_I]),
+         "dove_window_attention_tiles": (None, [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
          "dove_png_segment_rows": (C.c_int, [_I, _I]),
          "dove_png_bound": (C.c_size_t, [_I, _I, _I]),
          "dove_png_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I]),

@@ -2,7 +2,7 @@
 the tests and tools, the weights object that uploads itself once per device, the host tables that do the same, and the MLP half of a
 pre-LN transformer block.
 
-This module imports none of the metric modules; percep, flow, clipiqa, musiq, fastvqa and dover import it.  A metric module keeps the shapes of
+This module imports none of the metric modules; percep, flow, clipiqa, musiq, fastvqa, dover and maniqa import it.  A metric module keeps the shapes of
 its checkpoint, its packing (what is folded, fused or split) and the rule of its random draws."""
 from __future__ import annotations
 

@@ -1855,3 +1855,231 @@ def vqa_resized_view_f32(clip: torch.Tensor, frames: torch.Tensor, size, mean, s
                                                (C.c_double * 3)(*map(float, std)), int(bool(cols)), L.ptr(out), L.stream_ptr()),
             "dove_vqa_resized_view_f32")
     return out
+
+
+# ---- MANIQA (csrc/maniqa.hip): the batched strided GEMM, row softmax, 2-D window attention, crop gather, scale-add-transpose, fp64 head ----
+BMM_B_TRANSPOSED, BMM_STORE_TRANSPOSED, BMM_BIAS_ROWS = 1, 2, 4      # DOVE_BMM_* of include/dove_hip.h
+
+
+def _span(t: torch.Tensor) -> tuple:
+    """[first byte, past the last byte) of the memory a strided view reaches."""
+    if t.numel() == 0:
+        return t.data_ptr(), t.data_ptr()
+    return t.data_ptr(), t.data_ptr() + t.element_size() * (sum((n - 1) * s for n, s in zip(t.shape, t.stride())) + 1)
+
+
+def _overlap(a: torch.Tensor, b: torch.Tensor) -> bool:
+    (a0, a1), (b0, b1) = _span(a), _span(b)
+    return a0 < b1 and b0 < a1
+
+
+def _same_view(a: torch.Tensor, b: torch.Tensor) -> bool:
+    return a.data_ptr() == b.data_ptr() and a.shape == b.shape and a.stride() == b.stride()
+
+
+def _rows3(t: torch.Tensor, what: str, name: str):
+    """A float32 [B,R,C] or [R,C] operand with unit column stride -> (rows, cols, row stride, batch stride or None for a 2-D operand)."""
+    if t.dtype != torch.float32 or t.dim() not in (2, 3) or t.numel() == 0 or (t.shape[-1] > 1 and t.stride(-1) != 1) or \
+            (t.shape[-2] > 1 and t.stride(-2) < t.shape[-1]) or (t.dim() == 3 and t.stride(0) < 0):
+        raise ValueError(f"{what}: {name} {tuple(t.shape)} {t.dtype} with strides {t.stride()} must be float32 [B,R,C] or [R,C] rows")
+    ld = t.stride(-2) if t.shape[-2] > 1 else t.shape[-1]
+    return t.shape[-2], t.shape[-1], ld, (None if t.dim() == 2 else (t.stride(0) if t.shape[0] > 1 else 0))
+
+
+def bmm_f32_tiles() -> tuple:
+    """(M, N, K) tile of ``bmm_f32``'s kernel; needs no device."""
+    m, n, k = C.c_int(0), C.c_int(0), C.c_int(0)
+    L.load().dove_bmm_f32_tiles(C.byref(m), C.byref(n), C.byref(k))
+    return m.value, n.value, k.value
+
+
+def bmm_f32_kernel_name(b_transposed: bool = False, store_transposed: bool = False) -> str:
+    """The kernel ``bmm_f32`` runs for a layout; needs no device."""
+    return L.load().dove_bmm_f32_kernel_name(BMM_B_TRANSPOSED * bool(b_transposed) + BMM_STORE_TRANSPOSED * bool(store_transposed)).decode()
+
+
+def bmm_f32(a: torch.Tensor, b: torch.Tensor, *, b_transposed: bool = False, bias: torch.Tensor | None = None, bias_rows: bool = False,
+            residual: torch.Tensor | None = None, alpha: float = 1.0, store_transposed: bool = False,
+            out: torch.Tensor | None = None) -> torch.Tensor:
+    """Per batch, out = alpha (a b) (+ bias) (+ residual) in exact fp32 (csrc/maniqa.hip): every output is one fmaf chain over k ascending.
+    ``a`` float32 [B,M,K] or [M,K] rows, ``b`` [B,K,N] / [K,N] rows, or with ``b_transposed`` [B,N,K] / [N,K] rows (q k^T); row and batch
+    strides are free (multiples of 4; an expanded or 2-D operand is shared by the batch), K and N multiples of 4.  ``bias`` [N], or [M]
+    with ``bias_rows``.  ``store_transposed``: out and ``residual`` are [B,N,M].  ``residual`` may be ``out``; ``out`` must not alias
+    ``a`` or ``b``."""
+    _strided_on_device("bmm_f32", a, b)
+    M, K, lda, sa = _rows3(a, "bmm_f32", "a")
+    if b_transposed:
+        N, Kb, ldb, sb = _rows3(b, "bmm_f32", "b")
+    else:
+        Kb, N, ldb, sb = _rows3(b, "bmm_f32", "b")
+    batches = {t.shape[0] for t in (a, b) if t.dim() == 3}
+    if Kb != K or len(batches) > 1 or K % 4 or N % 4:
+        raise ValueError(f"bmm_f32: a {tuple(a.shape)} and b {tuple(b.shape)} (transposed: {bool(b_transposed)}) must agree in K and the batch, "
+                         f"K and N multiples of 4")
+    B = batches.pop() if batches else 1
+    sa, sb = sa or 0, sb or 0
+    if any(v % 4 for v in (lda, ldb, sa, sb)) or a.data_ptr() % 16 or b.data_ptr() % 16:
+        raise ValueError(f"bmm_f32: row strides {lda}, {ldb} and batch strides {sa}, {sb} must be multiples of 4 and a, b 16-byte aligned")
+    shape = (N, M) if store_transposed else (M, N)
+    if a.dim() == 3 or b.dim() == 3:
+        shape = (B,) + shape
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=a.device)
+    _strided_on_device("bmm_f32", out)
+    for name, t in (("out", out), ("residual", residual)):
+        if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_cuda):
+            raise ValueError(f"bmm_f32: {name} must be float32 {shape} on the device, got {t.dtype} {tuple(t.shape)}")
+    _, _, ldo, so = _rows3(out, "bmm_f32", "out")
+    if _overlap(out, a) or _overlap(out, b):
+        raise ValueError("bmm_f32: out must not alias a or b (every output reads a row of a and a column of b)")
+    ldr = sr = 0
+    if residual is not None:
+        _strided_on_device("bmm_f32", residual)
+        _, _, ldr, sr = _rows3(residual, "bmm_f32", "residual")
+        if _overlap(residual, out) and not _same_view(residual, out):
+            raise ValueError("bmm_f32: residual must not alias out unless it is out")
+    if bias is not None:
+        L.require_cuda(bias)
+        if bias.dtype != torch.float32 or bias.numel() != (M if bias_rows else N):
+            raise ValueError(f"bmm_f32: bias must be float32 [{M if bias_rows else N}], got {bias.dtype} {tuple(bias.shape)}")
+    flags = BMM_B_TRANSPOSED * bool(b_transposed) + BMM_STORE_TRANSPOSED * bool(store_transposed) + BMM_BIAS_ROWS * bool(bias is not None and bias_rows)
+    L.check(L.load().dove_bmm_f32(L.ptr(a), lda, sa, L.ptr(b), ldb, sb, L.ptr(bias), L.ptr(residual), ldr, sr or 0, L.ptr(out), ldo, so or 0, B, M, N,
+                                  K, float(alpha), flags, L.stream_ptr()), "dove_bmm_f32")
+    return out
+
+
+def softmax_rows_f32(x: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Softmax over the last axis of float32 [R,C] rows (any row stride): the true row maximum, the accurate expf, the row sum in a fixed
+    order (csrc/maniqa.hip).  ``out`` may be ``x``."""
+    _strided_on_device("softmax_rows_f32", x)
+    if x.dim() != 2:
+        raise ValueError(f"softmax_rows_f32: x {tuple(x.shape)} must be [R,C] rows")
+    R, Cc, ldx, _ = _rows3(x, "softmax_rows_f32", "x")
+    if out is None:
+        out = torch.empty(R, Cc, dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != (R, Cc) or (_overlap(out, x) and not _same_view(out, x)):
+        raise ValueError(f"softmax_rows_f32: out must be float32 {(R, Cc)} and x itself or apart from it")
+    _strided_on_device("softmax_rows_f32", out)
+    ldo = _rows3(out, "softmax_rows_f32", "out")[2]
+    L.check(L.load().dove_softmax_rows_f32(L.ptr(x), ldx, R, Cc, L.ptr(out), ldo, L.stream_ptr()), "dove_softmax_rows_f32")
+    return out
+
+
+def window_attention_tiles() -> tuple:
+    """(tile, longest window, widest head) of ``window_attention_f32``'s kernel; needs no device."""
+    t, n, d = C.c_int(0), C.c_int(0), C.c_int(0)
+    L.load().dove_window_attention_tiles(C.byref(t), C.byref(n), C.byref(d))
+    return t.value, n.value, d.value
+
+
+def window_attention_f32(qkv: torch.Tensor, heads: int, table: torch.Tensor, index: torch.Tensor, *, scale: float | None = None,
+                         region: torch.Tensor | None = None) -> torch.Tensor:
+    """qkv float32 [W,N,3 heads d] (q, k, v side by side; d a multiple of 32 up to 192, N <= 64), ``table`` float32 [R,heads], ``index``
+    int32 [N,N] -> float32 [W,N,heads d]: softmax(scale q k^T + table[index] + mask) v per window and head on the fp32 MFMA
+    (csrc/maniqa.hip).  ``region`` int32 [w,N] (w divides W: the windows of one sample): -100 between tokens of different ids.  ``scale``
+    defaults to 1 / sqrt(d)."""
+    L.require_cuda(qkv, table, index, region)
+    if qkv.dtype != torch.float32 or qkv.dim() != 3 or qkv.numel() == 0 or heads < 1 or qkv.shape[2] % (3 * heads):
+        raise ValueError(f"window_attention_f32: qkv {tuple(qkv.shape)} {qkv.dtype} must be float32 [W,N,3 heads d] for {heads} heads")
+    Wn, N, _ = qkv.shape
+    d = qkv.shape[2] // (3 * heads)
+    _, max_n, max_d = window_attention_tiles()
+    if N > max_n or d % 32 or d > max_d:
+        raise ValueError(f"window_attention_f32: windows of {N} tokens and heads of {d} (at most {max_n} tokens; heads a multiple of 32 up to {max_d})")
+    if table.dtype != torch.float32 or table.dim() != 2 or table.shape[1] != heads or table.shape[0] == 0:
+        raise ValueError(f"window_attention_f32: the bias table must be float32 [R,{heads}], got {table.dtype} {tuple(table.shape)}")
+    if index.dtype != torch.int32 or tuple(index.shape) != (N, N):
+        raise ValueError(f"window_attention_f32: index must be int32 {(N, N)}, got {index.dtype} {tuple(index.shape)}")
+    idw = 1
+    if region is not None:
+        if region.dtype != torch.int32 or region.dim() != 2 or region.shape[1] != N or region.shape[0] == 0 or Wn % region.shape[0]:
+            raise ValueError(f"window_attention_f32: region must be int32 [w,{N}] with w dividing {Wn}, got {region.dtype} {tuple(region.shape)}")
+        idw = region.shape[0]
+    D = heads * d
+    out = torch.empty(Wn, N, D, dtype=torch.float32, device=qkv.device)
+    L.check(L.load().dove_window_attention_f32(
+        L.ptr(qkv), C.c_void_p(qkv.data_ptr() + 4 * D), C.c_void_p(qkv.data_ptr() + 8 * D), 3 * D, Wn, N, heads, d,
+        1.0 / math.sqrt(d) if scale is None else float(scale), L.ptr(table), table.shape[0], L.ptr(index), L.ptr(region), idw, L.ptr(out), D,
+        L.stream_ptr()), "dove_window_attention_f32")
+    return out
+
+
+def maniqa_crops_f32(img: torch.Tensor, origins: torch.Tensor, side: int, patch: int) -> torch.Tensor:
+    """img: an [N,1|3,H,W] view (uint8 read as u / 255, float32 or bfloat16 in [0,1]; any strides, no copy), ``origins`` int32 [crops,2]
+    (row, column) on the device -> float32 [N crops (side / patch)^2, 3 patch^2]: every crop's (v - 0.5) / 0.5 in fp64, rounded once, as
+    the rows of the patch embedding's GEMM (column c patch^2 + dy patch + dx; csrc/maniqa.hip)."""
+    if img.dim() != 4 or img.shape[1] not in (1, 3) or not img.is_cuda:
+        raise ValueError(f"maniqa_crops_f32: need an [N,1|3,H,W] view on the HIP device, got {tuple(img.shape)} on {img.device}")
+    _strided_on_device("maniqa_crops_f32", img)
+    L.require_cuda(origins)
+    N, Cc, H, W = img.shape
+    if origins.dtype != torch.int32 or origins.dim() != 2 or origins.shape[1] != 2 or origins.shape[0] == 0:
+        raise ValueError("maniqa_crops_f32: origins must be int32 [crops,2]")
+    if patch < 1 or side < patch or side % patch or H < side or W < side:
+        raise ValueError(f"maniqa_crops_f32: crops of {side} (a multiple of the patch {patch}) do not fit a {H} x {W} frame")
+    crops, g = origins.shape[0], side // patch
+    out = torch.empty(N * crops * g * g, 3 * patch * patch, dtype=torch.float32, device=img.device)
+    if N == 0:
+        return out
+    v = _image_view(img)
+    L.check(L.load().dove_maniqa_crops_f32(C.byref(v), N, Cc, H, W, L.ptr(origins), crops, side, patch, L.ptr(out), L.stream_ptr()),
+            "dove_maniqa_crops_f32")
+    return out
+
+
+def maniqa_tokens_f32(emb: torch.Tensor, cls: torch.Tensor, pos: torch.Tensor) -> torch.Tensor:
+    """emb float32 [n T,D] patch embeddings, cls [D], pos [T + 1,D] -> float32 [n,T + 1,D]: cls + pos[0], then emb + pos[1 + t]."""
+    L.require_cuda(emb, cls, pos)
+    if any(t.dtype != torch.float32 for t in (emb, cls, pos)) or emb.dim() != 2 or pos.dim() != 2 or pos.shape[0] < 2 or \
+            pos.shape[1] != emb.shape[1] or cls.numel() != emb.shape[1] or emb.shape[0] == 0 or emb.shape[0] % (pos.shape[0] - 1):
+        raise ValueError(f"maniqa_tokens_f32: emb {tuple(emb.shape)} must be float32 [n T,D] with pos {tuple(pos.shape)} = [T + 1,D] and cls [D]")
+    T, D = pos.shape[0] - 1, emb.shape[1]
+    n = emb.shape[0] // T
+    out = torch.empty(n, T + 1, D, dtype=torch.float32, device=emb.device)
+    L.check(L.load().dove_maniqa_tokens_f32(L.ptr(emb), L.ptr(cls), L.ptr(pos), n, T, D, L.ptr(out), L.stream_ptr()), "dove_maniqa_tokens_f32")
+    return out
+
+
+def mix_f32(a: torch.Tensor, r: torch.Tensor | None = None, alpha: float = 1.0, transpose: bool = False,
+            out: torch.Tensor | None = None) -> torch.Tensor:
+    """out = alpha a (+ r), each step rounded on its own, on float32 [B,R,C] or [R,C] rows (free row and batch strides); ``transpose``:
+    out is [B,C,R].  Without ``transpose`` out may be ``a`` or ``r``; with it, it must be apart from both (csrc/maniqa.hip)."""
+    _strided_on_device("mix_f32", a)
+    R, Cc, lda, sa = _rows3(a, "mix_f32", "a")
+    B = a.shape[0] if a.dim() == 3 else 1
+    ldr = sr = 0
+    if r is not None:
+        _strided_on_device("mix_f32", r)
+        if r.shape != a.shape:
+            raise ValueError(f"mix_f32: r {tuple(r.shape)} must have a's shape {tuple(a.shape)}")
+        _, _, ldr, sr = _rows3(r, "mix_f32", "r")
+    shape = tuple(a.shape[:-2]) + ((Cc, R) if transpose else (R, Cc))
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=a.device)
+    elif tuple(out.shape) != shape:
+        raise ValueError(f"mix_f32: out must be float32 {shape}, got {tuple(out.shape)}")
+    _strided_on_device("mix_f32", out)
+    _, _, ldo, so = _rows3(out, "mix_f32", "out")
+    for t in (a, r):
+        if t is not None and _overlap(out, t) and (transpose or not _same_view(out, t)):
+            raise ValueError("mix_f32: out must not alias an input" + (" under transpose" if transpose else " unless it is that input"))
+    L.check(L.load().dove_mix_f32(L.ptr(a), lda, sa or 0, L.ptr(r), ldr, sr or 0, float(alpha), B, R, Cc, int(bool(transpose)), L.ptr(out), ldo,
+                                  so or 0, L.stream_ptr()), "dove_mix_f32")
+    return out
+
+
+def maniqa_score(hidden: torch.Tensor, wf: torch.Tensor, bf: torch.Tensor, ww: torch.Tensor, bw: torch.Tensor, want_crops: bool = False):
+    """hidden float32 [frames,crops,positions,2 hid] (the two branches' ReLU'd hidden units side by side), wf / ww float32 [hid], bf / bw
+    [1] -> float64 [frames]: per position f = relu(wf . h + bf), w = sigmoid(ww . h' + bw) in fp64; per crop sum f w / sum w; the mean
+    over a frame's crops, every sum in a fixed order.  ``want_crops``: also the crops' scores, float64 [frames,crops]."""
+    L.require_cuda(hidden, wf, bf, ww, bw)
+    if hidden.dtype != torch.float32 or hidden.dim() != 4 or hidden.numel() == 0 or hidden.shape[3] % 2:
+        raise ValueError(f"maniqa_score: hidden {tuple(hidden.shape)} {hidden.dtype} must be float32 [frames,crops,positions,2 hid]")
+    n, crops, T, two = hidden.shape
+    hid = two // 2
+    if any(t.dtype != torch.float32 for t in (wf, bf, ww, bw)) or wf.numel() != hid or ww.numel() != hid or bf.numel() != 1 or bw.numel() != 1:
+        raise ValueError(f"maniqa_score: need float32 wf [{hid}], bf [1], ww [{hid}], bw [1]")
+    out, per_crop = torch.empty(n, dtype=torch.float64, device=hidden.device), torch.empty(n, crops, dtype=torch.float64, device=hidden.device)
+    L.check(L.load().dove_maniqa_score(L.ptr(hidden), two, n, crops, T, hid, L.ptr(wf), L.ptr(bf), L.ptr(ww), L.ptr(bw), L.ptr(per_crop), L.ptr(out),
+                                       L.stream_ptr()), "dove_maniqa_score")
+    return (out, per_crop) if want_crops else out

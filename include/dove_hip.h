@@ -987,6 +987,54 @@ int dove_vqa_resized_view_f32(const dove_image_view* clip, int frames_in, int h,
                               int ymax, const int* xtab, const double* xw, int xmax, int oh, int ow, const double* mean, const double* std,
                               int cols, float* out, void* stream);
 
+/* MANIQA (csrc/maniqa.hip; tests/maniqa_ref.py is the definition): what the ViT-B/8 trunk, the transposed ("channel")
+ * attention and the 2-D Swin stages need beside the operators above.  fp32, no atomics, identical bits on repetition, a sample's result
+ * independent of the batch.  None needs a workspace.
+ *   bmm_f32: per batch i < batch, out_i = alpha (A_i B_i) (+ bias) (+ res_i) on v_mfma_f32_32x32x2_f32.  A_i = a + i sa is [m][k] rows of stride
+ *     lda; B_i = b + i sb is [k][n] rows of stride ldb, or with DOVE_BMM_B_TRANSPOSED [n][k] rows of stride ldb (q k^T).  A batch stride of 0
+ *     shares the operand.  k and n multiples of 4, m any; lda, ldb, sa, sb multiples of 4; a, b 16-byte aligned.  Every output is one fp32 fmaf
+ *     chain over k ascending whatever the shape, the tile and the batch (no split-K, no padded k), then, each step rounded on its own: times
+ *     alpha (when alpha != 1), plus bias[column] (bias[row] under DOVE_BMM_BIAS_ROWS), plus the residual.  out_i = out + i so has rows of stride
+ *     ldo; DOVE_BMM_STORE_TRANSPOSED stores element (row, column) at out_i[column ldo + row] and reads the residual (stride ldr, batch stride
+ *     sr) the same way.  res may be out; out must not overlap a or b.  dove_bmm_f32_tiles reports the 128 x 128 x 32 tile and
+ *     dove_bmm_f32_kernel_name the kernel a flag set runs; neither needs a device.
+ *   softmax_rows_f32: out[r] = softmax(x[r]) over cols columns (rows of stride ldx / ldo): the true row maximum, the accurate expf, the sum in
+ *     a fixed order, e / sum.  out may be x.
+ *   window_attention_f32: as swin3d_window_attention_f32 for 2-D windows with wider heads: `windows` windows of n <= 64 rows, head h in columns
+ *     [head_dim h, head_dim (h + 1)), head_dim a multiple of 32 up to 192; s = (q . k) scale + table[index[query][key]][h] + (region[query] !=
+ *     region[key] ? -100 : 0), out = softmax(s) v with the two-pass softmax.  One table, no fragment gate.  dove_window_attention_tiles
+ *     reports the 32-row tile, the longest window and the widest head.  K and V of a window are kept in LDS: 32 ceil(n / 32) (8 head_dim + 8) +
+ *     4 table_rows bytes must fit 128 KiB.
+ *   maniqa_crops_f32: img as above; crop k of frame f is the side x side square at origins[k] = (row, column) (int32 [crops][2] on the device,
+ *     clamped into the frame), (v - 0.5) / 0.5 in fp64 rounded once, written as the rows of the patch embedding's GEMM: out [n crops (side /
+ *     patch)^2][3 patch^2], column c patch^2 + (y % patch) patch + x % patch.  One channel is repeated.
+ *   maniqa_tokens_f32: out [n][tokens + 1][dim]: row 0 = cls + pos[0], row 1 + t = emb[n tokens + t] + pos[1 + t].
+ *   mix_f32: per batch, out = alpha a (+ r) on [rows][cols] matrices (strides lda, ldr, ldo, batch strides sa, sr, so), each step rounded on its
+ *     own; transpose != 0 stores out[col ldo + row] (out must then be neither input; otherwise out may be a or r).
+ *   maniqa_score: hidden [frames crops positions] rows of 2 hid at stride ld (the score branch's ReLU'd hidden units, then the weight
+ *     branch's); per position f = relu(wf . h + bf), w = sigmoid(ww . h' + bw) in fp64; crop_scores[frame crops + crop] = sum f w / sum w (fp64
+ *     [frames crops], an output of its own), out[frame] = the mean over its crops, every sum in a fixed order. */
+#define DOVE_BMM_B_TRANSPOSED 1
+#define DOVE_BMM_STORE_TRANSPOSED 2
+#define DOVE_BMM_BIAS_ROWS 4
+void dove_bmm_f32_tiles(int* m_tile, int* n_tile, int* k_tile);
+const char* dove_bmm_f32_kernel_name(int flags);
+int dove_bmm_f32(const float* a, long long lda, long long sa, const float* b, long long ldb, long long sb, const float* bias, const float* res,
+                 long long ldr, long long sr, float* out, long long ldo, long long so, int batch, int m, int n, int k, float alpha, int flags,
+                 void* stream);
+int dove_softmax_rows_f32(const float* x, long long ldx, long long rows, int cols, float* out, long long ldo, void* stream);
+void dove_window_attention_tiles(int* tile, int* max_n, int* max_head_dim);
+int dove_window_attention_f32(const float* q, const float* k, const float* v, long long ld, long long windows, int n, int heads, int head_dim,
+                              float scale, const float* table, int table_rows, const int* index, const int* region, int id_windows, float* out,
+                              long long ldo, void* stream);
+int dove_maniqa_crops_f32(const dove_image_view* img, int n, int c, int h, int w, const int* origins, int crops, int side, int patch, float* out,
+                          void* stream);
+int dove_maniqa_tokens_f32(const float* emb, const float* cls, const float* pos, long long n, int tokens, int dim, float* out, void* stream);
+int dove_mix_f32(const float* a, long long lda, long long sa, const float* r, long long ldr, long long sr, float alpha, int batch, int rows,
+                 int cols, int transpose, float* out, long long ldo, long long so, void* stream);
+int dove_maniqa_score(const float* hidden, long long ld, int frames, int crops, int positions, int hid, const float* wf, const float* bf,
+                      const float* ww, const float* bw, double* crop_scores, double* out, void* stream);
+
 /* ---- PNG encoder (csrc/png.hip; tests/png_ref.py is the bit-exact definition of the filtered stream) ----
  * png_encode: img is a strided [n,channels,h,w] view as above (channels 3 = RGB, 1 = grey; u8 as it is, f32 / bf16 quantised as
  *   dove_postprocess_u8 does, trunc(clamp(255 x, 0, 255))).  Frame i becomes a complete 8-bit, non-interlaced PNG file at
