@@ -11,7 +11,8 @@ calls ``pipe.enable_sequential_cpu_offload()`` like the reference (a no-op with 
 ``eval_metrics.py`` scores the saved files; the per-clip values go to ``metrics_<names>.json`` in ``--output_path`` (the reference's
 structure, ref :755-776); the registry's metrics that need weights take them from ``--metric_weights DIR`` (``--help`` lists the files); without it they, and always the other metrics of pyiqa, are refused; ``--dtype`` other than bfloat16 is refused.  Inputs are PNG folders,
 ``.npy`` clips (uint8 [F,H,W,3]) or ``.y4m`` files because H.264 decoding (decord) is outside the accelerated path; outputs are PNG
-folders, ``.npy`` or ``.y4m`` (``--y4m_save``; streamed chunk by chunk when ``--chunk_len > 0``).  ``--random_init`` builds the CogVideoX1.5-5B architecture with synthetic weights (no checkpoint is
+folders, ``.npy`` or ``.y4m`` (``--y4m_save``; streamed chunk by chunk when ``--chunk_len > 0``), or - encoded on the GPU, dove_amd.jpeg - ``.jpg`` folders
+(``--jpg_save``) or one Motion-JPEG ``.avi`` per clip at ``--fps`` (``--avi_save``), at ``--jpeg_quality`` and the subsampling of ``--save_format``.  ``--random_init`` builds the CogVideoX1.5-5B architecture with synthetic weights (no checkpoint is
 available offline).  ``--eval_psnr_dir`` computes plain PSNR (10*log10(1/MSE), per-frame mean) on the CPU against ground-truth folders; with it,
 ``psnr`` in ``--eval_metrics`` is that value and the other metrics use ``--gt_dir`` (or those folders without ``--gt_dir``)."""
 from __future__ import annotations
@@ -27,14 +28,15 @@ def add_model_arguments(ap):
     ap.add_argument("--model_path", type=str, default=None)
     ap.add_argument("--lora_path", type=str, default=None, help="LoRA weights to fuse into the transformer (ref :613-621)")
     ap.add_argument("--random_init", action="store_true")
-    ap.add_argument("--fps", type=int, default=16, help="frame rate of the Y4M file (--y4m_save; ref :521); PNG / .npy frame files carry none")
+    ap.add_argument("--fps", type=int, default=16, help="frame rate of the Y4M file (--y4m_save) or the Motion-JPEG AVI (--avi_save; ref :521); PNG / JPEG / .npy frame files carry none")
     ap.add_argument("--dtype", type=str, default="bfloat16")
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--upscale_mode", type=str, default="bilinear", help="ref :527, :672; 'bilinear' is the fused HIP kernel, others run torch's interpolate")
     ap.add_argument("--upscale", type=int, default=4)
     ap.add_argument("--is_cpu_offload", action="store_true", help="ref :533, :637-641: enable_sequential_cpu_offload() (a no-op here)")
     ap.add_argument("--save_format", type=str, default="yuv444p",
-                    help="pixel format of the Y4M file (--y4m_save): yuv444p, yuv422p or yuv420p (ref :541); unused otherwise")
+                    help="pixel format of the Y4M file (--y4m_save): yuv444p, yuv422p or yuv420p (ref :541); chroma subsampling of "
+                         "--jpg_save / --avi_save: yuv444p (4:4:4) or yuv420p (4:2:0); unused otherwise")
     ap.add_argument("--noise_step", type=int, default=0)
     ap.add_argument("--sr_noise_step", type=int, default=399)
     ap.add_argument("--is_vae_st", action="store_true")
@@ -155,6 +157,15 @@ def _save_clip_y4m(out, video, pads, args, path, chroma, color_fix, need_frames)
     return prepost.load_frames(path, yuv_matrix=args.yuv_matrix) if need_frames else None
 
 
+def jpeg_subsampling(save_format: str) -> str:
+    """--save_format -> the subsampling of --jpg_save / --avi_save; refused only where a JPEG is written."""
+    table = {"yuv444p": "444", "yuv420p": "420"}
+    if save_format not in table:
+        raise ValueError(f"--save_format {save_format}: --jpg_save / --avi_save write yuv444p (4:4:4) or yuv420p (4:2:0); 4:2:2 JPEG is not "
+                         "built")
+    return table[save_format]
+
+
 def build_parser() -> argparse.ArgumentParser:
     from . import metrics as M
     ap = argparse.ArgumentParser(description="VSR using DOVE on MI355X (dove_amd)")
@@ -172,6 +183,10 @@ def build_parser() -> argparse.ArgumentParser:
                     help="who writes the --png_save files: PIL on the host, or the GPU encoder (dove_amd.png)")
     ap.add_argument("--y4m_save", action="store_true",
                     help="write <clip>.y4m (YUV4MPEG2) with --fps and --save_format; with --chunk_len > 0 it is streamed chunk by chunk")
+    ap.add_argument("--jpg_save", action="store_true", help="write <clip>/000.jpg, ... (baseline JPEG encoded on the GPU, dove_amd.jpeg)")
+    ap.add_argument("--avi_save", action="store_true",
+                    help="write <clip>.avi (Motion-JPEG in RIFF AVI 1.0 at --fps; the frames are encoded on the GPU, dove_amd.jpeg / dove_amd.avi)")
+    ap.add_argument("--jpeg_quality", type=int, default=95, help="libjpeg quality 1..100 of --jpg_save / --avi_save")
     ap.add_argument("--eval_psnr_dir", type=str, default=None)
     add_model_arguments(ap)
     return ap
@@ -189,6 +204,14 @@ def main(argv=None):
     metric_weights = eval_metrics.load_weights(metrics, args.metric_weights)
     metrics_gt = args.gt_dir or args.eval_psnr_dir
     y4m_chroma = None
+    forms = [f for f in ("png_save", "y4m_save", "jpg_save", "avi_save") if getattr(args, f)]
+    if len(forms) > 1 and forms != ["png_save", "y4m_save"]:
+        raise ValueError(" and ".join("--" + f for f in forms) + ": choose one output form")
+    jpeg_sub = None
+    if args.jpg_save or args.avi_save:
+        if not 1 <= args.jpeg_quality <= 100:
+            raise ValueError(f"--jpeg_quality {args.jpeg_quality} is not in 1..100")
+        jpeg_sub = jpeg_subsampling(args.save_format)
     if args.y4m_save:
         if args.png_save:
             raise ValueError("--y4m_save and --png_save: choose one output form")
@@ -202,6 +225,9 @@ def main(argv=None):
     if args.y4m_save:
         print(f"[dove_amd] clips are written as .y4m (YUV4MPEG2, {args.save_format}, {args.fps} fps, {args.yuv_matrix} / "
               f"{args.yuv_range or 'limited'}); --eval_metrics score the frames decoded from that file")
+    elif args.jpg_save or args.avi_save:
+        print(f"[dove_amd] clips are written as " + (f"Motion-JPEG .avi at {args.fps} fps" if args.avi_save else ".jpg folders") +
+              f" (baseline JPEG, quality {args.jpeg_quality}, {args.save_format}); --eval_metrics score the frames before JPEG coding")
     elif not args.png_save:
         print(f"[dove_amd] clips are written as .npy frame arrays (uint8 [F,H,W,3]); --fps {args.fps} / --save_format {args.save_format} "
               "apply to the reference's mp4 writer only")
@@ -253,6 +279,12 @@ def main(argv=None):
             pass
         elif args.png_save:
             prepost.save_frames_as_png(frames_out, os.path.join(args.output_path, stem), encoder=args.png_encoder)
+        elif args.jpg_save:
+            prepost.save_frames_as_jpeg(frames_out, os.path.join(args.output_path, stem), args.jpeg_quality, jpeg_sub)
+        elif args.avi_save:
+            from . import jpeg
+            jpeg.save_avi(frames_out, os.path.join(args.output_path, stem + ".avi"), fps=args.fps, quality=args.jpeg_quality,
+                          subsampling=jpeg_sub)
         else:
             import numpy as np
             np.save(os.path.join(args.output_path, stem + ".npy"), frames_out.cpu().numpy())

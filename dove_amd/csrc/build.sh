@@ -5,7 +5,7 @@ cd "$(dirname "$0")"
 if [ $# -ne 0 ]; then echo "build.sh takes no arguments (got: $*)" >&2; exit 2; fi
 OUT=../libdove_hip.so
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result"
-SRCS="capi igemm igemm_legacy norm attention attention_pipe attention_mx elementwise mxfp8 t5 graph metrics colorfix yuv video degrade conv_f32 flow percep niqe clipiqa musiq swin3d convnext3d maniqa png vcodec"
+SRCS="capi igemm igemm_legacy norm attention attention_pipe attention_mx elementwise mxfp8 t5 graph metrics colorfix yuv video degrade conv_f32 flow percep niqe clipiqa musiq swin3d convnext3d maniqa png jpeg vcodec"
 pids=()
 for f in $SRCS; do
   hipcc $FLAGS -c $f.hip -o $f.o &

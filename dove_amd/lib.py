@@ -294,6 +294,8 @@ SIGNATURES = {
     # PNG encoder (csrc/png.hip): whole files on the device, and its deflate stage on a plain buffer
     "dove_png_encode": [C.POINTER(ImageView), _I, _I, _I, _I, _VP, C.c_size_t, _VP, _VP, _VP],
     "dove_zlib_huffman": [_VP, _LL, _LL, _VP, C.c_size_t, _VP, _VP, _VP],
+    # JPEG encoder (csrc/jpeg.hip): whole baseline JFIF files on the device
+    "dove_jpeg_encode": [C.POINTER(ImageView), _I, _I, _I, C.POINTER(C.c_int), _I, _VP, C.c_size_t, _VP, _VP, _VP],
 }
 PLAIN = {"dove_last_error": (C.c_char_p, []), "dove_abi_version": (C.c_int, []), "dove_comm_destroy": (None, [C.c_void_p]),
          "dove_conv_gn_partial_rows": (C.c_longlong, [C.POINTER(ConvDesc)]),
@@ -337,7 +339,10 @@ PLAIN = {"dove_last_error": (C.c_char_p, []), "dove_abi_version": (C.c_int, []),
          "dove_png_bound": (C.c_size_t, [_I, _I, _I]),
          "dove_png_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I]),
          "dove_zlib_huffman_bound": (C.c_size_t, [_LL, _LL]),
-         "dove_zlib_huffman_workspace_bytes": (C.c_size_t, [_LL, _LL])}
+         "dove_zlib_huffman_workspace_bytes": (C.c_size_t, [_LL, _LL]),
+         "dove_jpeg_restart_mcus": (C.c_int, []),
+         "dove_jpeg_bound": (C.c_size_t, [_I, _I, _I]),
+         "dove_jpeg_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I])}
 
 
 def kernel_source_sha256() -> str:

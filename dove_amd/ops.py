@@ -818,6 +818,50 @@ def zlib_huffman(data: torch.Tensor, segment_bytes: int = 32768):
     return out, size
 
 
+JPEG_SUBSAMPLING = {"420": 0, "444": 1}                             # DOVE_JPEG_* of include/dove_hip.h
+
+
+def jpeg_subsampling_code(subsampling) -> int:
+    """'420' / '444' (or the DOVE_JPEG_* code itself) -> the code.  Host code: anything else raises ValueError."""
+    if isinstance(subsampling, int) and not isinstance(subsampling, bool) and subsampling in JPEG_SUBSAMPLING.values():
+        return subsampling
+    if subsampling not in JPEG_SUBSAMPLING:
+        raise ValueError(f"jpeg subsampling {subsampling!r}: one of {sorted(JPEG_SUBSAMPLING)}")
+    return JPEG_SUBSAMPLING[subsampling]
+
+
+def jpeg_restart_mcus() -> int:
+    """MCUs in one restart interval of the JPEG encoder (host function)."""
+    return int(L.load().dove_jpeg_restart_mcus())
+
+
+def jpeg_bound(h: int, w: int, subsampling="444") -> int:
+    """The most bytes one encoded h x w file can take (host function; 0 for a bad shape)."""
+    return int(L.load().dove_jpeg_bound(h, w, jpeg_subsampling_code(subsampling)))
+
+
+def jpeg_encode(frames: torch.Tensor, quality=95, subsampling="444"):
+    """frames: a [N,3,H,W] RGB view (any strides, no copy; uint8, or float32 / bfloat16 in [0,1]) -> (files uint8 [N, jpeg_bound], sizes
+    int64 [N]) on the device: row i holds one complete baseline JFIF file in its first sizes[i] bytes (csrc/jpeg.hip).  ``quality``:
+    1..100, a number or one per frame; ``subsampling``: '444' or '420'."""
+    if frames.dim() != 4 or frames.shape[1] != 3:
+        raise ValueError(f"jpeg_encode: frames {tuple(frames.shape)} must be a [N,3,H,W] view")
+    if not frames.is_cuda:
+        raise RuntimeError("jpeg_encode needs its input on the HIP device (`cuda`); there is no CPU path")
+    sub = jpeg_subsampling_code(subsampling)
+    N, _, H, W = frames.shape
+    lib = L.load()
+    with torch.cuda.device(frames.device):
+        out = torch.empty(N, int(lib.dove_jpeg_bound(H, W, sub)), dtype=torch.uint8, device=frames.device)
+        sizes = torch.empty(N, dtype=torch.int64, device=frames.device)
+        if N:
+            ws = torch.empty(max(int(lib.dove_jpeg_workspace_bytes(N, H, W, sub)), 16), dtype=torch.uint8, device=frames.device)
+            v = _image_view(frames)
+            L.check(lib.dove_jpeg_encode(C.byref(v), N, H, W, _per_frame(quality, N, C.c_int, "jpeg_encode"), sub, L.ptr(ws), ws.numel(),
+                                         L.ptr(out), L.ptr(sizes), L.stream_ptr()), "dove_jpeg_encode")
+    return out, sizes
+
+
 def randn(shape, seed: int, stream_id: int = 0, dtype=torch.float32, offset: int = 0, device="cuda") -> torch.Tensor:
     """Standard normals of the library's counter-based generator (csrc/video.hip ``dove_randn``: Philox4x32-10 keyed by ``seed``, counter
     (element / 4, ``stream_id``), Box-Muller; tests/randn_ref.py is the definition): the elements [offset, offset + numel) of stream

@@ -119,3 +119,9 @@ def save_frames_as_png(frames_u8: torch.Tensor, output_dir: str, encoder: str = 
     os.makedirs(output_dir, exist_ok=True)
     for i, fr in enumerate(frames_u8.cpu().numpy()):
         Image.fromarray(fr).save(os.path.join(output_dir, f"{i:03d}.png"))
+
+
+def save_frames_as_jpeg(frames_u8: torch.Tensor, output_dir: str, quality: int = 95, subsampling: str = "444"):
+    """``{i:03d}.jpg`` files, the PNG saver's naming, encoded on the GPU (dove_amd.jpeg; there is no host encoder behind this)."""
+    from . import jpeg
+    jpeg.save_frames(frames_u8, output_dir, quality=quality, subsampling=subsampling)

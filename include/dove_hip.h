@@ -1060,6 +1060,27 @@ size_t dove_zlib_huffman_workspace_bytes(long long nbytes, long long segment_byt
 int dove_zlib_huffman(const unsigned char* in, long long nbytes, long long segment_bytes, void* ws, size_t ws_bytes, unsigned char* out,
                       long long* size, void* stream);
 
+/* ---- JPEG encoder (csrc/jpeg.hip; tests/jpeg_ref.py is the byte-exact definition of the file) ----
+ * jpeg_encode: img is a strided [n,3,h,w] RGB view as above (u8 as it is, f32 / bf16 quantised as dove_postprocess_u8 does,
+ *   trunc(clamp(255 x, 0, 255))).  Frame i becomes a complete baseline JFIF file at out + i * dove_jpeg_bound(h, w, subsampling), sizes[i]
+ *   bytes long (sizes is on the device): SOI, APP0 (JFIF 1.01, density 1:1), two DQT, SOF0, the four Annex-K Huffman tables, DRI, SOS,
+ *   the entropy-coded data, EOI.  Colour conversion, the 2x2 chroma mean of 4:2:0, the integer DCT and the quantiser under libjpeg's
+ *   quality rule are those of dove_jpeg_roundtrip (quality is a HOST array of n entries, 1..100); 4:4:4 skips the chroma mean and pads to
+ *   whole 8 x 8 instead of 16 x 16.  AC levels are clamped to -1023..1023 and DC levels to -1024..1023 after the quantiser (never binding
+ *   for 8-bit samples).  The scan is cut into restart intervals of dove_jpeg_restart_mcus() MCUs: each resets the DC predictors, is padded
+ *   with 1-bits to a byte, has 0x00 after every 0xFF data byte and is followed by RST(m mod 8), the last one by EOI.
+ *   dove_jpeg_bound = 629 header bytes + 416 per 8 x 8 block (at most 22 + 63 * 26 = 1660 bits, 208 bytes with padding, doubled by
+ *   stuffing) + 2 per interval: a true upper bound, far above real files (0 for a bad shape or subsampling; h, w <= 65535).
+ *   ws: device scratch of dove_jpeg_workspace_bytes(n, h, w, subsampling) bytes, 16-byte aligned.  Integer arithmetic only: two calls
+ *   give identical bytes and a frame's file does not depend on the batch it is encoded in. */
+#define DOVE_JPEG_420 0
+#define DOVE_JPEG_444 1
+int dove_jpeg_restart_mcus(void);
+size_t dove_jpeg_bound(int h, int w, int subsampling);
+size_t dove_jpeg_workspace_bytes(int n, int h, int w, int subsampling);
+int dove_jpeg_encode(const dove_image_view* img, int n, int h, int w, const int* quality, int subsampling, void* ws, size_t ws_bytes,
+                     unsigned char* out, long long* sizes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
